@@ -8,14 +8,18 @@ layers, 250 M parameters), bs = 8 items x K = 7 options = 56 pairs, 80 tokens x 
 train mode (dropout on), one step = forward + MLM/MVM/ranking/traj losses + backward + (all-reduce) + fused AdamW + LR step,
 exactly the body of the reference's train_epoch (utils/utils_init.py:199-239).  Inputs are synthetic and resident in HBM.
 
-Prints ONE JSON line (rank 0).  Besides the driver contract it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the driver contract (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (see
+dump_outputs).  Everything else is measured only under --full, where the line also carries
   roofline     -- the dominant kernel (fp32 MFMA GEMM): algorithmic FLOPs of its launches / their HIP-event time, measured
                   live on the launch stream during the timed steps, against the 157.3 TFLOP/s fp32 matrix peak;
   variants     -- (N = 1, default precision only; NOT the headline) the same captured step re-timed with the opt-in fp32x3 projections
                   (fp32 operands, three exact bf16 terms per value, six bf16 MFMAs per product; LABNOTES.md 5a) and with bf16 operands
                   (the arithmetic of BASELINE configs[4]); --no-variants skips them;
   cpu_baseline -- the CPU oracle (a port of the reference's path, oracle/vilbert_ref.py) timed on this box's host cores
-                  on a bounded sample of the same workload (rank 0, N = 1 only).
+                  on a bounded sample of the same workload (rank 0, N = 1 only);
+  host_probe, power, data_parallel, config.replica_checksum_spread -- host enqueue probe steps, package power over the timed steps,
+                  the N > 1 exchange diagnostics and replica check.
 
 N > 1: `python bench.py --gpus N` starts its own N ranks (re-exec under torch.distributed.run on 127.0.0.1) unless a launcher already
 exported WORLD_SIZE; one rank per GPU, gradients summed over RCCL/xGMI through the C ABI's communicator (ytvln_rccl_*).
@@ -65,6 +69,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg2_full_pretrain_bs8", choices=sorted(WORKLOADS))
     ap.add_argument("--bs", type=int, default=None, help="override items per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check besides the headline (CPU baseline, variants, per-kernel roofline timing, host "
+                         "probe, power sampling, N > 1 exchange diagnostics); the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; samples of large arrays)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the extra (non-headline) fp32x3 / bf16 measurements of the default run")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -87,8 +96,8 @@ def parse():
     ap.add_argument("--kernel-table", action="store_true", help="print per-shape GEMM timing to stderr")
     ap.add_argument("--eval-dropout-off", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--host-probe", type=int, default=3, metavar="N",
-                    help="N extra steps after the timed region (0: none), each enqueued into EMPTY queues (device synchronised first): wall and "
-                         "CPU time of the enqueue alone = the host work of a step without back-pressure waits (tools/host8.py)")
+                    help="(--full) N extra steps after the timed region (0: none), each enqueued into EMPTY queues (device synchronised first): wall "
+                         "and CPU time of the enqueue alone = the host work of a step without back-pressure waits (tools/host8.py)")
     ap.add_argument("--host-wait", choices=["blocking", "spin", "lean"], default="blocking",
                     help="blocking (default): hipDeviceScheduleBlockingSync + the host paced two steps ahead of the device on blocking events "
                          "(ytvln.misc.set_host_wait / StepPacer): a rank sleeps while its GPU works -- <= one core per rank; spin: the runtime's "
@@ -108,7 +117,11 @@ def parse():
     ap.add_argument("--dp-selftest", action="store_true",
                     help="(diagnostic, not a measurement configuration) run the N > 1 code path -- DataParallel wrapper, two-graph step, RCCL "
                          "all-reduce of the whole gradient arena through the C ABI communicator -- in a ONE-rank world on a single GPU")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:              # a plain run does only what the headline needs
+        a.no_cpu_baseline = a.no_variants = a.no_kernel_timing = True
+        a.host_probe = 0
+    return a
 
 
 def make_args(flags):
@@ -385,6 +398,50 @@ def cpu_baseline(workload, budget_s: float = 45.0):
                       f"after {1 if len(times) > 1 else 0} warm-up ({med:.2f} s/step)"}
 
 
+DUMP_SAMPLE = 1 << 22            # elements per sampled array: three samples stay well inside 64 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def flat_sample(tensors, n: int, seed: int) -> np.ndarray:
+    """float32 host copy of a fixed, seeded sample of the concatenation of `tensors` (in the given order): every element when they hold at
+    most n, else the sorted distinct positions of n seeded draws -- the same positions for every build with the same tensor sizes."""
+    sizes = [t.numel() for t in tensors]
+    total = sum(sizes)
+    if total <= n:
+        return torch.cat([t.detach().reshape(-1).float() for t in tensors]).cpu().numpy()
+    idx = np.unique(np.random.default_rng(seed).integers(0, total, n))
+    out, lo = [], 0
+    for t, s in zip(tensors, sizes):
+        a, b = np.searchsorted(idx, [lo, lo + s])
+        if b > a:
+            out.append(t.detach().reshape(-1)[torch.from_numpy(idx[a:b] - lo).to(t.device)].float())
+        lo += s
+    return torch.cat(out).cpu().numpy()
+
+
+def dump_outputs(path: str, loss, model=None, opt=None, ranking=None) -> dict:
+    """What a caller of the timed step holds after its last step, as float32 .npy files under `path`: the loss; for training the
+    parameters and AdamW's two moments (seeded samples, in named_parameters() order; moments of the parameters that have them); for
+    inference the ranking scores.  Returns {name: array}."""
+    outs = {"loss": np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32)}
+    if ranking is not None:
+        outs["ranking"] = ranking.detach().float().cpu().numpy()
+    if model is not None:
+        params = [p for _, p in model.named_parameters()]
+        outs["params_sample"] = flat_sample(params, DUMP_SAMPLE, seed=0)
+        if opt is not None:
+            st = [opt.state[p] for p in params if "exp_avg" in opt.state.get(p, {})]
+            if st:
+                outs["adamw_exp_avg_sample"] = flat_sample([s["exp_avg"] for s in st], DUMP_SAMPLE, seed=1)
+                outs["adamw_exp_avg_sq_sample"] = flat_sample([s["exp_avg_sq"] for s in st], DUMP_SAMPLE, seed=2)
+    nbytes = sum(v.nbytes for v in outs.values())
+    assert nbytes <= DUMP_LIMIT_BYTES, f"dump of {nbytes} bytes exceeds {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, v in outs.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return outs
+
+
 class stdout_to_stderr:
     """File-descriptor level: native libraries (gloo's connection notice, RCCL's version banner under NCCL_DEBUG=INFO) print to fd 1 while
     they initialise; the bench's stdout carries exactly ONE JSON line."""
@@ -466,7 +523,7 @@ def main():
     collective = D.default_collective()
     dp_wrap = world > 1 or a.dp_selftest
     rccl_log = None
-    if dp_wrap and os.environ.get("YTVLN_BENCH_RCCL_INFO", "1") != "0" and "NCCL_DEBUG" not in os.environ:
+    if a.full and dp_wrap and os.environ.get("YTVLN_BENCH_RCCL_INFO", "1") != "0" and "NCCL_DEBUG" not in os.environ:
         # the N > 1 line explains itself: RCCL's own choice of algorithm / protocol for the gradient all-reduce, read back from its log
         # (a FILE: the bench's stdout carries exactly one JSON line)
         rccl_log = f"/tmp/ytvln_rccl_{os.getpid()}.log"
@@ -538,13 +595,15 @@ def main():
         ftimer.install()
 
     infer = a.workload.startswith("infer")
+    last_ranking = [None]
     if infer:
         model.eval()
         inputs = utils_init.get_model_input(batch, True)
 
         def step(i):      # forward only (test.py:144-166): scores of the candidate paths stay on the device
             with torch.no_grad():
-                return runner(*inputs)["ranking"].sum(), None
+                last_ranking[0] = runner(*inputs)["ranking"]
+                return last_ranking[0].sum(), None
     else:
         def step(i):
             return utils_init.train_step(runner, opt, sched, batch, args, i, all_options=True, loss_aware_heads=a.loss_aware_heads)
@@ -695,7 +754,7 @@ def main():
         for i in range(2):                         # the upload / assembly buffers are new: let the allocator settle before timing
             step(a.warmup + i)
         torch.cuda.synchronize()
-    power = PowerSampler(dev) if rank == 0 else None
+    power = PowerSampler(dev) if rank == 0 and a.full else None
     if power is not None:
         power.start()
     pace_mode, pace_depth = a.pace.split(":")
@@ -736,6 +795,8 @@ def main():
                           reverse=True)[:4]          # the four busiest threads of this rank during the timed region: ms of CPU per step, name
     timer.on = ftimer.on = False
     elapsed = control_reduce(elapsed, dist.ReduceOp.MAX)
+    if a.dump_outputs and rank == 0:          # before anything below runs another step
+        dump_outputs(a.dump_outputs, loss, model=None if infer else model, opt=None if infer else opt, ranking=last_ranking[0])
     host_probe = None
     if a.host_probe > 0:
         pw, pc, pd = [], [], []
@@ -758,12 +819,12 @@ def main():
     # data parallel: after the timed steps every replica must hold the same parameters (each rank saw different data, so this holds only
     # if every gradient was exchanged): max - min over ranks of a checksum of all parameters, 0.0 when the replicas are bit-identical
     replica_spread = None
-    if dp_wrap and not infer:
+    if a.full and dp_wrap and not infer:
         with torch.no_grad():
             chk = float(sum(p.detach().double().sum() for p in model.parameters()))
         replica_spread = control_reduce(chk, dist.ReduceOp.MAX) - control_reduce(chk, dist.ReduceOp.MIN)
     dp_diag = None
-    if dp_wrap and not infer:
+    if a.full and dp_wrap and not infer:
         dp_diag = {}
         try:
             flat = opt.flat_grad()
@@ -1022,7 +1083,7 @@ def main():
             try:
                 import subprocess
                 torch.cuda.empty_cache()
-                cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cfg5_long_traj_bs32", "--precision", "bf16", "--no-variants",
+                cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cfg5_long_traj_bs32", "--precision", "bf16", "--full", "--no-variants",
                        "--no-cpu-baseline", "--steps", "4", "--warmup", "2"]
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
                 c5 = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -1047,7 +1108,7 @@ def main():
                 try:
                     import subprocess
                     torch.cuda.empty_cache()
-                    cmd = [sys.executable, os.path.abspath(__file__), "--workload", a.workload, "--no-variants", "--no-cpu-baseline", "--no-kernel-timing",
+                    cmd = [sys.executable, os.path.abspath(__file__), "--workload", a.workload, "--full", "--no-variants", "--no-cpu-baseline", "--no-kernel-timing",
                            "--host-probe", "0", "--steps", "8", "--warmup", "3"] + extra
                     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300)
                     c = json.loads(r.stdout.decode().strip().splitlines()[-1])

@@ -283,3 +283,52 @@ def test_bench_self_launch_command(monkeypatch, n):
     assert argv[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and f"--nproc-per-node={n}" in argv
     assert argv[argv.index("--master-addr") + 1] == "127.0.0.1" and int(argv[argv.index("--master-port") + 1]) > 0
     assert argv[-6:] == ["--gpus", str(n), "--steps", "2", "--warmup", "1"] and argv[-7].endswith("bench.py")
+
+
+def _bench_module():
+    import importlib
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    return importlib.import_module("bench")
+
+
+def test_bench_plain_run_switches_off_the_extra_measurements(monkeypatch):
+    """Without --full the bench times the headline only; --full keeps every extra measurement on, each --no-* option still switches one off."""
+    import sys
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.steps == 5 and a.warmup == 2 and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_variants and a.no_kernel_timing and a.host_probe == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-variants", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.no_variants and not a.no_cpu_baseline and not a.no_kernel_timing and a.host_probe == 3 and a.dump_outputs == "out"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files; seeded samples that pick the same positions of the concatenated tensors every time; AdamW moments
+    only of the parameters that have them."""
+    import numpy as np
+    bench = _bench_module()
+    torch.manual_seed(0)
+    model = nn.Sequential(nn.Linear(40, 30), nn.Linear(30, 5), nn.Linear(5, 2))
+    model[2].weight.requires_grad_(False)
+    opt = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-3)
+    loss = model(torch.randn(8, 40)).square().mean()
+    loss.backward()
+    opt.step()
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 300)
+    outs = bench.dump_outputs(str(tmp_path / "d"), loss, model=model, opt=opt)
+    assert sorted(os.listdir(tmp_path / "d")) == ["adamw_exp_avg_sample.npy", "adamw_exp_avg_sq_sample.npy", "loss.npy", "params_sample.npy"]
+    for k, v in outs.items():
+        assert np.load(tmp_path / "d" / (k + ".npy")).dtype == np.float32 and np.array_equal(np.load(tmp_path / "d" / (k + ".npy")), v)
+    assert float(outs["loss"]) == float(loss.detach())
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.size, 300))
+    assert np.array_equal(outs["params_sample"], flat[idx])
+    m = torch.cat([opt.state[p]["exp_avg"].reshape(-1) for p in model.parameters() if p.requires_grad]).numpy()
+    assert m.size == flat.size - 10 and np.array_equal(outs["adamw_exp_avg_sample"], m[np.unique(np.random.default_rng(1).integers(0, m.size, 300))])
+    small = bench.flat_sample([torch.arange(7.0), torch.arange(3.0)], 300, seed=5)           # fewer elements than the sample: all of them
+    assert np.array_equal(small, np.r_[np.arange(7.0), np.arange(3.0)].astype(np.float32))
+    assert np.array_equal(bench.flat_sample(list(model.parameters()), 300, 0), outs["params_sample"])

@@ -239,7 +239,7 @@ def _run_bench(extra, env_extra, timeout=900):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1_tiny_mlm_bs2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-variants", *extra], capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-variants", *extra], capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -32,7 +32,7 @@ def launch(i, n):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29610 + i), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                YTVLN_BENCH_RCCL_INFO="0", PYTORCH_HIP_ALLOC_CONF="expandable_segments:False")
     mine = cores[i * cpr:(i + 1) * cpr]
-    cmd = ["taskset", "-c", ",".join(map(str, mine)), sys.executable, os.path.join(ROOT, "bench.py"), "--dp-selftest", "--no-variants",
+    cmd = ["taskset", "-c", ",".join(map(str, mine)), sys.executable, os.path.join(ROOT, "bench.py"), "--dp-selftest", "--full", "--no-variants",
            "--no-cpu-baseline", "--no-kernel-timing", "--steps", str(steps), "--warmup", "3", "--host-probe", "8"]
     err = open(os.path.join(ROOT, "gpurun_out", f"host8_rank{i}_of{n}.err"), "w")
     return subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=err, text=True), mine
