@@ -340,6 +340,13 @@ int ytvln_adamw_f32(float* p, const float* g, float* m, float* v, const void* ch
  * path are refreshed by the optimizer step itself (+2 bytes per parameter, no cast pass) */
 int ytvln_adamw_f32_bf16copy(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, const void* chunks, int nchunks,
                              const float* hyper, float grad_scale, void* stream);
+/* the same step reading bf16 gradients (the bf16 data-parallel exchange: the SUM over ranks, rounded to bf16, at the arena's offsets):
+ * g = float(g_bf16) * grad_scale, otherwise bit-identical to ytvln_adamw_f32 fed the widened values.  p_bf16 may be NULL (no weight copy). */
+int ytvln_adamw_f32_gbf16(float* p, const uint16_t* g_bf16, float* m, float* v, uint16_t* p_bf16, const void* chunks, int nchunks,
+                          const float* hyper, float grad_scale, void* stream);
+/* g_bf16[o : o+len] = bf16(g[o : o+len]) (round to nearest even) for every record of an AdamW chunk table: the send buffer of the bf16
+ * exchange, one workgroup per record; elements outside the table are not written.  Both bases 16-byte aligned. */
+int ytvln_grad_pack_bf16(const float* g, uint16_t* g_bf16, const void* chunks, int nchunks, void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI ------------------------------------------------------------------------
  * Replaces DistributedDataParallel over NCCL (utils/distributed.py:63-104: init_process_group("nccl") + DDP's bucketed all-reduce).
@@ -363,8 +370,8 @@ int ytvln_rccl_allreduce(void* comm, void* buf, int64_t count, int dtype, int op
  * arena as ONE RCCL group: the buckets of an optimizer step without a host round trip between them. */
 int ytvln_rccl_allreduce_slices_f32(void* comm, float* base, const int64_t* offsets, const int64_t* counts, int nslices,
                                     void* stream);
-/* the same for an arena of any element type of the enum above (offsets / counts in ELEMENTS): the bf16 gradient exchange of the bf16-resident
- * path (BASELINE configs[4]) moves half the bytes of the fp32 one over xGMI */
+/* the same for an arena of any element type of the enum above (offsets / counts in ELEMENTS): with YTVLN_DT_BF16, the opt-in bf16 gradient
+ * exchange (ytvln_grad_pack_bf16 -> this -> ytvln_adamw_f32_gbf16) moves half the bytes of the fp32 one over xGMI */
 int ytvln_rccl_allreduce_slices(void* comm, void* base, int dtype, const int64_t* offsets, const int64_t* counts, int nslices,
                                 void* stream);
 /* in-place byte broadcast from `root` (DDP's rank-0 weight broadcast at wrap time) */

@@ -13,13 +13,17 @@ point-to-point xGMI fabric rather than a translation of DDP's defaults:
   * the never-used tensors (q_dense*, bi_seq_relationship, unflagged heads) are simply absent from the
     arena, so no `find_unused_parameters` graph walk is needed and the bucket layout is identical on all ranks;
   * buckets are all-reduced (SUM) as soon as their last gradient has been accumulated during backward (post-accumulate
-    hooks), on RCCL's own stream; the 1/world_size averaging is folded into the fused AdamW kernel (`grad_scale`).
+    hooks), on RCCL's own stream; the 1/world_size averaging is folded into the fused AdamW kernel (`grad_scale`);
+  * opt-in (`grad_dtype="bf16"` / YTVLN_DP_GRAD_DTYPE=bf16, DDP's bf16 compression hook): gradients still accumulate in the fp32
+    arena, each exchanged range is rounded to bf16 into a send buffer of the same offsets (AdamW.grad_bf16()), summed over the
+    ranks in bf16, and the fused AdamW reads the bf16 sums -- half the bytes over xGMI.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
 import os
+import struct
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -28,6 +32,7 @@ from torch import nn
 
 from . import _lib
 from . import ops as _ops
+from .optimization import CHUNK
 
 
 def get_rank(default: int = 0) -> int:
@@ -110,6 +115,17 @@ def init_distributed(backend: Optional[str] = None, force: bool = False) -> Tupl
     return dist.get_rank(), dist.get_world_size()
 
 
+def grad_exchange_dtype(value=None) -> torch.dtype:
+    """The element type of the gradient exchange: `value` ("fp32" / "bf16" / torch.float32 / torch.bfloat16), or with None the variable
+    YTVLN_DP_GRAD_DTYPE (default fp32).  bf16 is opt-in: the sums are rounded, results differ from the fp32 exchange."""
+    if value is None:
+        value = os.environ.get("YTVLN_DP_GRAD_DTYPE", "fp32")
+    dt = {"fp32": torch.float32, "bf16": torch.bfloat16, torch.float32: torch.float32, torch.bfloat16: torch.bfloat16}.get(value)
+    if dt is None:
+        raise ValueError(f"gradient exchange dtype {value!r}: expected 'fp32' or 'bf16' (torch.float32 / torch.bfloat16)")
+    return dt
+
+
 _TORCH_DT = {torch.float32: _lib.DT_F32, torch.float64: _lib.DT_F64, torch.bfloat16: _lib.DT_BF16, torch.int64: _lib.DT_I64,
              torch.uint8: _lib.DT_U8}
 _RED = {"sum": _lib.RED_SUM, "max": _lib.RED_MAX, "min": _lib.RED_MIN}
@@ -175,14 +191,18 @@ class RcclCommunicator:
         return t
 
     def all_reduce_slices(self, flat: torch.Tensor, slices: Sequence[Tuple[int, int]], stream=None) -> None:
-        """SUM over ranks of flat[lo:hi] for every (lo, hi), issued as one RCCL group."""
+        """SUM over ranks of flat[lo:hi] for every (lo, hi) (elements), issued as one RCCL group.  fp32: ytvln_rccl_allreduce_slices_f32;
+        any other dtype of the C ABI (the bf16 exchange buffer): ytvln_rccl_allreduce_slices."""
         self._check(flat)
-        if flat.dtype != torch.float32:
-            raise RuntimeError("gradient arenas are fp32")
+        if flat.dtype not in _TORCH_DT:
+            raise RuntimeError(f"all_reduce_slices: unsupported dtype {flat.dtype}")
         n = len(slices)
         offs = (ctypes.c_int64 * n)(*[lo for lo, _ in slices])
         cnts = (ctypes.c_int64 * n)(*[hi - lo for lo, hi in slices])
-        _lib.call("ytvln_rccl_allreduce_slices_f32", self._handle, flat.data_ptr(), offs, cnts, n, self._stream(stream))
+        if flat.dtype == torch.float32:
+            _lib.call("ytvln_rccl_allreduce_slices_f32", self._handle, flat.data_ptr(), offs, cnts, n, self._stream(stream))
+        else:
+            _lib.call("ytvln_rccl_allreduce_slices", self._handle, flat.data_ptr(), _TORCH_DT[flat.dtype], offs, cnts, n, self._stream(stream))
 
     def broadcast(self, t: torch.Tensor, root: int = 0, stream=None) -> torch.Tensor:
         self._check(t)
@@ -224,6 +244,8 @@ class GradBucketReducer:
     behind an event recorded where its last gradient landed, and `finish()` makes the consumer's stream wait on the bucket events
     (no host synchronisation).  `comm=None`: torch.distributed.all_reduce(async_op=True) -- device-agnostic, tested on CPU with
     gloo at world_size 2.  `always` runs the collectives even in a one-rank world (single-GPU tests of the RCCL path).
+    `send` (the bf16 exchange, AdamW.grad_bf16()): a ready bucket is first rounded into send[lo:hi] (ytvln_grad_pack_bf16, on the stream of
+    its collective) and that bf16 view is what is all-reduced; `flat` keeps the local fp32 gradients.
 
     Contract (DDP reduces on every backward; this reducer exchanges a bucket ONCE per optimizer step): with several backward
     passes per step, all but the last must run with the exchange disabled (`DataParallel.no_sync()`, which
@@ -232,8 +254,11 @@ class GradBucketReducer:
 
     def __init__(self, flat: torch.Tensor, layout: Sequence[Tuple[torch.nn.Parameter, int, int]], bucket_bytes: int = 256 << 20,
                  group=None, overlap: bool = True, enabled_fn: Optional[Callable[[], bool]] = None,
-                 comm: Optional[RcclCommunicator] = None, always: bool = False):
+                 comm: Optional[RcclCommunicator] = None, always: bool = False, send: Optional[torch.Tensor] = None):
         self.flat, self.group, self.overlap, self.comm = flat, group, overlap, comm
+        self.send = send
+        if send is not None and (send.numel() != flat.numel() or not flat.is_cuda):
+            raise RuntimeError("bf16 exchange: the send buffer must match the gradient arena on a HIP device")
         self.enabled_fn = enabled_fn or (lambda: True)
         self._offsets = {id(p): off for p, off, _ in layout}
         self.world = comm.world if comm is not None else (dist.get_world_size(group) if dist.is_initialized() else 1)
@@ -253,6 +278,9 @@ class GradBucketReducer:
         for b in self.buckets:
             for p in b["params"]:
                 self._of[id(p)] = b
+            if send is not None:        # pack table of the bucket: CHUNK-element records, as the AdamW tables (one workgroup each)
+                rec = b"".join(struct.pack("<qqff", o, min(CHUNK, b["hi"] - o), 0.0, 0.0) for o in range(b["lo"], b["hi"], CHUNK))
+                b["pack"] = (torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(flat.device), len(rec) // 24)
         self._hooks = []
         self._late: Optional[str] = None
         self.reset()
@@ -269,17 +297,22 @@ class GradBucketReducer:
         if not self.active:
             return
         self.collectives += 1
-        view = self.flat[b["lo"]:b["hi"]]
+        view = (self.flat if self.send is None else self.send)[b["lo"]:b["hi"]]
         _ops.TwoStream.gather_streams()     # two-stream mode: a bucket holds gradients of both sides; this hook runs on the stream of ONE
         if self.comm is not None:
             ready = torch.cuda.Event()
             ready.record()                                   # on the stream that produced the bucket's last gradient
             self.comm_stream.wait_event(ready)
+            if self.send is not None:
+                with torch.cuda.stream(self.comm_stream):
+                    _ops.grad_pack_bf16(self.flat, self.send, *b["pack"])
             self.comm.all_reduce(view, "sum", stream=self.comm_stream)
             done = torch.cuda.Event()
             done.record(self.comm_stream)
             b["handle"] = done
         else:
+            if self.send is not None:
+                _ops.grad_pack_bf16(self.flat, self.send, *b["pack"])
             b["handle"] = dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     def _on_grad(self, p):
@@ -316,6 +349,12 @@ class GradBucketReducer:
             else:
                 b["handle"].wait()
         self.reset()
+
+    def payload_bytes(self) -> int:
+        """Bytes one rank contributes to the exchange per optimizer step: elements of every bucket x element size of what travels."""
+        if not self.active:
+            return 0
+        return sum(b["hi"] - b["lo"] for b in self.buckets) * (self.flat if self.send is None else self.send).element_size()
 
     def remove(self):
         for h in self._hooks:
@@ -367,11 +406,21 @@ class DataParallel(nn.Module):
 
     collective: "rccl" (default on a HIP device) -- the C ABI's own communicator (`RcclCommunicator`); "torch" --
     `torch.distributed` collectives on `group` (gloo in the CPU tests).  `always_exchange` keeps the collectives running in a one-rank
-    world (they are the identity there): how the single-GPU tests drive the RCCL path."""
+    world (they are the identity there): how the single-GPU tests drive the RCCL path.
+
+    grad_dtype: element type of the exchange -- None reads YTVLN_DP_GRAD_DTYPE (`fp32`, the default, or `bf16`); "fp32" / "bf16" /
+    torch.float32 / torch.bfloat16 (`grad_exchange_dtype`).  bf16 rounds each rank's fp32 gradients to bf16, sums them in bf16 and lets
+    the fused AdamW read the sums (DDP's bf16 compression hook): half the bytes, results differ from the fp32 exchange.  HIP modules and
+    ytvln's AdamW only; every rank must choose the same (compared at wrap time)."""
 
     def __init__(self, module: nn.Module, bucket_bytes: int = 256 << 20, group=None, broadcast: bool = True,
-                 collective: Optional[str] = None, always_exchange: bool = False, comm: Optional[RcclCommunicator] = None):
+                 collective: Optional[str] = None, always_exchange: bool = False, comm: Optional[RcclCommunicator] = None,
+                 grad_dtype=None):
         super().__init__()
+        self.grad_dtype = grad_exchange_dtype(grad_dtype)
+        if self.grad_dtype == torch.bfloat16 and not all(p.is_cuda for p in module.parameters()):
+            raise RuntimeError("DataParallel(grad_dtype=bf16): the pack and the bf16-gradient update are HIP kernels; the module is not on a "
+                               "HIP device (there is no CPU path)")
         self.module = module
         self.group, self.bucket_bytes = group, bucket_bytes
         self.collective = collective or ("rccl" if comm is not None else default_collective())
@@ -383,6 +432,13 @@ class DataParallel(nn.Module):
             self.comm = RcclCommunicator.from_process_group(params[0].device, group)
         self.world = self.comm.world if self.comm is not None else (dist.get_world_size(group) if dist.is_initialized() else 1)
         self.always_exchange = always_exchange
+        if self.world > 1 and dist.is_initialized():
+            # ranks exchanging in different dtypes would meet in mismatched collectives (a hang): compare on the control plane first
+            every = [None] * dist.get_world_size(group)
+            dist.all_gather_object(every, str(self.grad_dtype), group=group)
+            if len(set(every)) != 1:
+                raise RuntimeError(f"DataParallel: the ranks chose different gradient exchange dtypes {every} (grad_dtype / "
+                                   "YTVLN_DP_GRAD_DTYPE): refusing to start the exchange")
         self._reducer: Optional[GradBucketReducer] = None
         self._opt = None
         self.require_backward_grad_sync = True
@@ -426,7 +482,26 @@ class DataParallel(nn.Module):
         self._opt = optimizer
         optimizer.grad_scale = 1.0 / self.world
         optimizer.grad_sync = self._sync
+        if self.bf16_exchange and not hasattr(optimizer, "grad_bf16"):
+            raise RuntimeError("DataParallel(grad_dtype=bf16) needs ytvln.optimization.AdamW (it owns the bf16 exchange buffer)")
+        optimizer.exchange_dtype = torch.bfloat16 if self.bf16_exchange else torch.float32
         return self
+
+    @property
+    def exchanging(self) -> bool:
+        return self.world > 1 or self.always_exchange
+
+    @property
+    def bf16_exchange(self) -> bool:
+        """Gradients travel as bf16: bf16 chosen AND there is an exchange (a one-rank world without `always_exchange` rounds nothing)."""
+        return self.grad_dtype == torch.bfloat16 and self.exchanging
+
+    def exchange_bytes_per_step(self) -> Optional[int]:
+        """Payload of the gradient exchange per optimizer step (elements exchanged x element size; 0 without an exchange; None before the
+        first optimizer step has laid out the buckets)."""
+        if not self.exchanging:
+            return 0
+        return None if self._reducer is None else self._reducer.payload_bytes()
 
     def _sync(self, flat: torch.Tensor, layout):
         if self.world == 1 and not self.always_exchange:
@@ -436,7 +511,8 @@ class DataParallel(nn.Module):
                 self._reducer.remove()
             self._reducer = GradBucketReducer(flat, layout, self.bucket_bytes, self.group,
                                               enabled_fn=lambda: self.require_backward_grad_sync,
-                                              comm=self.comm, always=self.always_exchange)
+                                              comm=self.comm, always=self.always_exchange,
+                                              send=self._opt.grad_bf16() if self.bf16_exchange else None)
         self._reducer.finish()
 
     def all_reduce_(self, t: torch.Tensor, op: str = "sum") -> torch.Tensor:
@@ -472,6 +548,10 @@ class GraphedTrainStep:
     The host enqueues a handful of graph launches and RCCL groups per step instead of ~1500 kernels, so N processes do not compete for host
     cores; no watchdog thread, no hidden stream.
 
+    With the bf16 exchange of the wrapped DataParallel (`grad_dtype`) every form packs what it exchanges into the optimizer's bf16 buffer
+    right before the collective (split: at the end of graph A; single: inside the graph; phased: per group on the communication stream),
+    all-reduces the bf16 slices and runs AdamW on the bf16 sums.
+
     `fwd_bwd(backward=None)` must run forward + backward only (utils_init.train_step(..., optimizer_step=False, backward=backward)) on
     STATIC input tensors and return the loss tensor; refill the inputs in place between steps.  Run >= 1 eager step first (arenas,
     allocator warm-up)."""
@@ -483,6 +563,8 @@ class GraphedTrainStep:
         self.comm = dp.comm if dp is not None else None
         self.world = dp.world if dp is not None else (dist.get_world_size(group) if dist.is_initialized() else 1)
         self.exchange = self.world > 1 or (dp is not None and dp.always_exchange)
+        self.grad_dtype = dp.grad_dtype if (dp is not None and self.exchange) else torch.float32
+        self.bf16 = self.grad_dtype == torch.bfloat16
         # default: the phased backward (exchange under the rest of backward) whenever there is an exchange and the C ABI's communicator
         # to run it on its own stream; otherwise the two-graph form with the exchange between the graphs
         explicit = mode or os.environ.get("YTVLN_DP_GRAPH")
@@ -499,10 +581,15 @@ class GraphedTrainStep:
             raise RuntimeError("run at least one eager training step before capturing")
         optimizer.zero_grad()
         optimizer.grad_scale = 1.0 / self.world
+        optimizer.exchange_dtype = self.grad_dtype
         if _ops.get_matmul_precision() == "bf16" and hasattr(optimizer, "bf16_arena"):
             optimizer.bf16_arena()          # the one-time cast of the whole weight arena happens here, eagerly: not recorded into a graph
+        if self.bf16:
+            optimizer.grad_bf16()           # the exchange buffer is allocated eagerly, outside the graphs' pools
         torch.cuda.synchronize()
         flat = optimizer.flat_grad()
+        # the buffer the collectives work on: the fp32 arena, or its bf16 copy (same offsets; slices stay element ranges)
+        self._xbuf = optimizer.grad_bf16() if self.bf16 else flat
         cap = max(1, bucket_bytes // flat.element_size())
         self._slices = [(lo, min(lo + cap, flat.numel())) for lo in range(0, flat.numel(), cap)]
         if dp is not None:
@@ -517,9 +604,11 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.graph_a, capture_error_mode="thread_local"):
                 self.loss = fwd_bwd()
                 optimizer.capture_adopt()
+                if self.bf16:
+                    optimizer.pack_grads()
                 if self.mode == "single":
                     if self.exchange:
-                        self.comm.all_reduce_slices(flat, self._slices)
+                        self.comm.all_reduce_slices(self._xbuf, self._slices)
                     optimizer.capture_update()
             self.graph_b = None
             if self.mode == "split":
@@ -533,11 +622,13 @@ class GraphedTrainStep:
             torch.cuda.synchronize()
 
     def layout_digest(self) -> str:
-        """What every rank must agree on before the first grouped collective: the step form, the arena size and the exact slice lists."""
+        """What every rank must agree on before the first grouped collective: the step form, the arena size, the exact slice lists and the
+        exchange dtype."""
         import hashlib
         flat = self.opt.flat_grad()
+        dtype = getattr(self, "grad_dtype", torch.float32)
         desc = repr((self.mode, int(flat.numel()) if flat is not None else -1, self._slices,
-                     getattr(self, "_group_slices", None), self.world))
+                     getattr(self, "_group_slices", None), self.world) + ((str(dtype),) if dtype != torch.float32 else ()))
         return hashlib.sha256(desc.encode()).hexdigest()
 
     def verify_layout_across_ranks(self):
@@ -670,6 +761,13 @@ class GraphedTrainStep:
         self._comm_stream = torch.cuda.Stream()
         self._events = [torch.cuda.Event() for _ in graphs]
 
+    def exchange_bytes_per_step(self) -> int:
+        """Payload of the gradient exchange per step: elements all-reduced x element size of the exchange dtype (0 without an exchange)."""
+        if not self.exchange:
+            return 0
+        slices = self._slices if self.mode != "phased" else [sl for g in self._group_slices for sl in g]
+        return sum(hi - lo for lo, hi in slices) * self._xbuf.element_size()
+
     def exposed_exchange_ms(self) -> Optional[float]:
         """With `self.profile = True`: milliseconds of the LAST step during which the compute stream had nothing left to do but wait for
         the gradient exchange (phased: from the end of the last backward graph to the end of the last RCCL group; split: the whole
@@ -690,7 +788,7 @@ class GraphedTrainStep:
             # also reads its weight last, so nothing that still runs touches them).  Both hide under the following phases; what stays
             # exposed is the last group's exchange and its share of the update.
             cur = torch.cuda.current_stream()
-            flat = self.opt.flat_grad()
+            xbuf = self._xbuf
             self.opt.prepare_replay()                   # hyper-parameters of this step: uploaded before the first per-group update
             tables = self.opt.group_tables(self._group_slices, owner=self)
             overlap = self.comm is not None or not self.exchange          # (torch.distributed data plane: everything in stream order)
@@ -699,14 +797,19 @@ class GraphedTrainStep:
                 if not self._group_slices[k]:
                     continue
                 if not overlap:
+                    if self.bf16:
+                        self.opt.pack_grads(tables[k])
                     for lo, hi in self._group_slices[k]:
-                        dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
+                        dist.all_reduce(xbuf[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
                     self.opt.launch_tables(tables[k])
                     continue
                 self._events[k].record(cur)
                 self._comm_stream.wait_event(self._events[k])
+                if self.bf16:
+                    with torch.cuda.stream(self._comm_stream):
+                        self.opt.pack_grads(tables[k])
                 if self.exchange:
-                    self.comm.all_reduce_slices(flat, self._group_slices[k], stream=self._comm_stream)
+                    self.comm.all_reduce_slices(xbuf, self._group_slices[k], stream=self._comm_stream)
                 if prof and k == len(self.graphs) - 1:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(cur)
@@ -726,15 +829,15 @@ class GraphedTrainStep:
         else:
             self.graph_a.replay()
             if self.exchange:
-                flat = self.opt.flat_grad()
+                xbuf = self._xbuf
                 if prof:
                     e0 = torch.cuda.Event(enable_timing=True)
                     e0.record()
                 if self.comm is not None:
-                    self.comm.all_reduce_slices(flat, self._slices)
+                    self.comm.all_reduce_slices(xbuf, self._slices)
                 else:
                     for lo, hi in self._slices:
-                        dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
+                        dist.all_reduce(xbuf[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
                 if prof:
                     e1 = torch.cuda.Event(enable_timing=True)
                     e1.record()

@@ -1665,3 +1665,21 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, chunks: Tensor, nchun
         return
     call("ytvln_adamw_f32", _ptr(p), _ptr(g), _ptr(m), _ptr(v), chunks.data_ptr(), int(nchunks), _ptr(hyper), float(grad_scale),
          _stream())
+
+
+def adamw_step_gbf16(p: Tensor, g_bf16: Tensor, m: Tensor, v: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor, grad_scale: float = 1.0,
+                     p_bf16: Optional[Tensor] = None):
+    """adamw_step reading bf16 gradients (the sums of the bf16 data-parallel exchange, same offsets as the fp32 arena): bit-identical to
+    adamw_step fed `g_bf16.float()`."""
+    for t, nme in ((p, "p"), (m, "m"), (v, "v"), (hyper, "hyper")):
+        _check(t, nme)
+    _check(g_bf16, "g_bf16", torch.bfloat16)
+    call("ytvln_adamw_f32_gbf16", _ptr(p), g_bf16.data_ptr(), _ptr(m), _ptr(v), None if p_bf16 is None else p_bf16.data_ptr(), chunks.data_ptr(),
+         int(nchunks), _ptr(hyper), float(grad_scale), _stream())
+
+
+def grad_pack_bf16(g: Tensor, g_bf16: Tensor, chunks: Tensor, nchunks: int):
+    """g_bf16[o:o+len] = g[o:o+len].to(bfloat16) for every record (offset, length, ...) of an AdamW chunk table, on the current stream."""
+    _check(g, "g")
+    _check(g_bf16, "g_bf16", torch.bfloat16)
+    call("ytvln_grad_pack_bf16", _ptr(g), g_bf16.data_ptr(), chunks.data_ptr(), int(nchunks), _stream())

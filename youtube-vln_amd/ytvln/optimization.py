@@ -104,6 +104,9 @@ class AdamW(Optimizer):
         self._arena = None          # dict(p, g, m, v flat tensors; index: id(param) -> (offset, numel))
         self._launch = None         # list of launch classes
         self.grad_scale = 1.0       # multiplied into the gradient inside the kernel (set by data-parallel wrappers)
+        # torch.bfloat16 (set by data-parallel wrappers with the bf16 exchange): the update reads the bf16 exchange buffer (grad_bf16()),
+        # not the fp32 arena.  Local accumulation stays fp32 either way.
+        self.exchange_dtype = torch.float32
 
     # ---- arena management -----------------------------------------------------------------------------------------
     def _members(self):
@@ -144,7 +147,7 @@ class AdamW(Optimizer):
                 p.grad = flat["g"][o:o + n].view(p.shape)
                 st["exp_avg"] = flat["m"][o:o + n].view(p.shape)
                 st["exp_avg_sq"] = flat["v"][o:o + n].view(p.shape)
-        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={})
+        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None)
         self._launch = None
         del old
         # let the weight-gradient GEMMs write straight into the gradient arena and the packed projections alias the
@@ -181,6 +184,36 @@ class AdamW(Optimizer):
                         ops.call("ytvln_cast_f32_bf16", a["p"].data_ptr() + 4 * o, n, 1, n, a["pb"].data_ptr() + 2 * o, n, ops._stream())
                 vers[id(p)] = p._version
         return a["pb"]
+
+    def grad_bf16(self):
+        """The send / receive buffer of the bf16 gradient exchange: bf16, the size and offsets of the fp32 gradient arena, allocated on first
+        use (zeros: the padding between slots stays zero) and dropped with the arena.  Not part of state_dict.  None before the arena
+        exists."""
+        a = self._arena
+        if a is None:
+            return None
+        if a["gb"] is None:
+            with ops.TwoStream.shared_write():
+                a["gb"] = torch.zeros(a["g"].numel(), dtype=torch.bfloat16, device=a["g"].device)
+        return a["gb"]
+
+    def pack_grads(self, tables=None):
+        """Round the fp32 gradients to bf16 into grad_bf16(), on the current stream: over the chunk tables of every launch class (None) or
+        over `tables` = [(launch class index, chunk table, number of chunks)] (one group of group_tables())."""
+        gb = self.grad_bf16()
+        if tables is None:
+            tables = [(ci, c["table"], c["n"]) for ci, c in enumerate(self._launch)]
+        for _, table, n in tables:
+            ops.grad_pack_bf16(self._arena["g"], gb, table, n)
+
+    def _update(self, table, n, hyper):
+        a = self._arena
+        if self.exchange_dtype == torch.bfloat16:
+            if a["gb"] is None:
+                raise RuntimeError("bf16 gradient exchange: the update would read a bf16 buffer nothing was packed into")
+            ops.adamw_step_gbf16(a["p"], a["gb"], a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
+        else:
+            ops.adamw_step(a["p"], a["g"], a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
 
     def _ensure_arena(self):
         members = self._members()
@@ -264,9 +297,8 @@ class AdamW(Optimizer):
                 self.state[p]["step"] = t
 
     def _launch_kernels(self):
-        a = self._arena
         for c in self._launch:
-            ops.adamw_step(a["p"], a["g"], a["m"], a["v"], c["table"], c["n"], c["hyper"], self.grad_scale, p_bf16=a["pb"])
+            self._update(c["table"], c["n"], c["hyper"])
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -371,9 +403,8 @@ class AdamW(Optimizer):
 
     def launch_tables(self, tables):
         """The fused AdamW kernels of one group, on the current stream (hyper-parameters come from prepare_replay())."""
-        a = self._arena
         for ci, table, n in tables:
-            ops.adamw_step(a["p"], a["g"], a["m"], a["v"], table, n, self._launch[ci]["hyper"], self.grad_scale, p_bf16=a["pb"])
+            self._update(table, n, self._launch[ci]["hyper"])
 
     def finish_group_step(self):
         """After the last group of a step: gradients are consumed, arena slots may be written directly again."""
