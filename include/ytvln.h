@@ -57,6 +57,13 @@ enum {
     YTVLN_EPI_MUL_DGELU = 3,  /* C = (A.B) * gelu'(aux)      backward of EPI_GELU through the next Linear        */
     YTVLN_EPI_MUL_DRELU = 4   /* C = (A.B) * (aux > 0)       backward of EPI_RELU (aux = the forward output)     */
 };
+/* activation selector of the stand-alone activation kernels (ytvln_act_fwd_*, ytvln_act_bwd_*) ONLY, not a GEMM epilogue: ytvln_gemm_f32 /
+ * ytvln_gemm_bf16 reject it.  swish(z) = z * sigmoid(z) (vilbert.py:122-123) is unfused by design: y = swish(x W^T + b) is the GEMM with
+ * YTVLN_EPI_NONE writing the pre-activation z (kept for the backward, as EPI_GELU keeps aux), then ytvln_act_fwd_*.  Against a fused epilogue
+ * that is one extra read and one extra write of [rows, N] per activated projection (8 bytes per element in fp32, 4 in bf16). */
+enum {
+    YTVLN_ACT_SWISH = 5
+};
 
 /* Dense projection on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).  Replaces every nn.Linear / F.linear on the path
  * (vilbert.py:285-287, 322, 352, 365, 555-568, 641-644, 831, 864, 906, 968, 1358 ...) and their autograd backward.
@@ -214,8 +221,16 @@ int ytvln_image_embed_fwd_f32(const float* img, const float* loc, const float* W
                               const float* beta, float* y, float* s_out, float* mean, float* rstd, int64_t rows,
                               int H, float eps, float p_post, const int64_t* rng, int64_t site, void* stream);
 
-/* dz = dy * act'(aux) elementwise (act = YTVLN_EPI_GELU: aux is the pre-activation; YTVLN_EPI_RELU: aux is the output). */
+/* dz = dy * act'(aux) elementwise (act = YTVLN_EPI_GELU: aux is the pre-activation; YTVLN_EPI_RELU: aux is the output; YTVLN_ACT_SWISH: aux is
+ * the pre-activation z, act' = s + z s (1 - s) with s = sigmoid(z)).  Pointers 16-byte aligned; YTVLN_ACT_SWISH also takes unaligned ones
+ * (one element per lane then). */
 int ytvln_act_bwd_f32(const float* dy, const float* aux, float* dz, int64_t n, int act, void* stream);
+
+/* y = act(z) elementwise for the one activation that is not a GEMM epilogue: act = YTVLN_ACT_SWISH, y = z * sigmoid(z) (vilbert.py:122-123; the
+ * forward of BertIntermediate / BertPredictionHeadTransform, vilbert.py:351-354, 864-866, with hidden_act = "swish").  Any n >= 0, y == z allowed
+ * (in place); 16 bytes per lane when both pointers are 16-byte aligned, one element per lane otherwise.  Finite for every finite input
+ * (sigmoid is formed from exp(-|z|) <= 1).  Other values of act are rejected: gelu / relu stay GEMM epilogues. */
+int ytvln_act_fwd_f32(const float* z, float* y, int64_t n, int act, void* stream);
 
 /* y = x * keep / (1 - p): nn.Dropout forward and (applied to dy) backward (lily.py:100). */
 int ytvln_dropout_f32(const float* x, float* y, int64_t n, float p, const int64_t* rng, int64_t site, void* stream);
@@ -235,7 +250,10 @@ int ytvln_image_embed_fwd_bf16(const uint16_t* img, const float* loc, const floa
                                const float* W2, const float* b2, const float* E, const float* gamma, const float* beta, uint16_t* y,
                                uint16_t* s_out, float* mean, float* rstd, int64_t rows, int H, float eps, float p_post, const int64_t* rng,
                                int64_t site, void* stream);
+/* ytvln_act_bwd_bf16: gelu / relu need 8-byte aligned pointers and n % 4 == 0; YTVLN_ACT_SWISH takes any n and alignment.  ytvln_act_fwd_bf16: as
+ * ytvln_act_fwd_f32 on bf16 elements (widened on load, fp32 arithmetic, rounded to nearest even on store). */
 int ytvln_act_bwd_bf16(const uint16_t* dy, const uint16_t* aux, uint16_t* dz, int64_t n, int act, void* stream);
+int ytvln_act_fwd_bf16(const uint16_t* z, uint16_t* y, int64_t n, int act, void* stream);
 
 /* Fused multi-head attention on the fp32 matrix cores, flash-style (scores never reach HBM).  One entry point serves
  * BertSelfAttention (vilbert.py:284-311), BertImageSelfAttention (:413-440) and both directions of BertBiAttention

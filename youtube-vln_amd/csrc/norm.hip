@@ -624,6 +624,69 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 }
 
 // ---- elementwise --------------------------------------------------------------------------------------------------
+// swish(z) = z * sigmoid(z) (vilbert.py:122-123) and its derivative s + z s (1 - s).  The two halves of the sigmoid, p = e / (1 + e) <= 1/2
+// and q = 1 / (1 + e) >= 1/2 with e = exp(-|z|) <= 1, are both formed from the one small exponential: no quotient can become inf / inf or
+// 0 * inf, 1 - s carries no cancellation (it IS the other half), and |z| p <= |z| exp(-|z|) < 0.37.  z = -1e4: e = 0, swish = -0.0, derivative 0;
+// z = +1e4: swish = z, derivative 1.  expf and the division are the accurate ones (the fp32 kernels owe the reference 1e-6).
+__device__ __forceinline__ void sigmoid_halves(float z, float& p, float& q) {
+    const float e = expf(-fabsf(z));
+    q = 1.0f / (1.0f + e);
+    p = e * q;
+}
+__device__ __forceinline__ float swish_f(float z) {
+    float p, q;
+    sigmoid_halves(z, p, q);
+    return z * (z < 0.f ? p : q);
+}
+__device__ __forceinline__ float dswish_f(float z) {
+    float p, q;
+    sigmoid_halves(z, p, q);
+    return fmaf(z * p, q, z < 0.f ? p : q);
+}
+__device__ __forceinline__ float4 swish4(float4 z) { return make_float4(swish_f(z.x), swish_f(z.y), swish_f(z.z), swish_f(z.w)); }
+__device__ __forceinline__ float4 mul_dswish4(float4 d, float4 z) {
+    return make_float4(d.x * dswish_f(z.x), d.y * dswish_f(z.y), d.z * dswish_f(z.z), d.w * dswish_f(z.w));
+}
+__device__ __forceinline__ float bf1(const bf16_t* p, int64_t i) { return __uint_as_float((uint32_t)p[i] << 16); }
+
+// y = swish(z), the unfused activation behind a plain GEMM (gelu / relu are GEMM epilogues and never come here).  y == z is allowed: every
+// lane reads exactly the elements it writes (no __restrict__ on the pair).  VEC: 16 bytes per lane over the first n & ~3 (fp32) / n & ~7 (bf16)
+// elements, block 0 finishes the tail one element per lane; !VEC (a base pointer off the 16-byte grid): one element per lane throughout.
+template <bool VEC>
+__global__ __launch_bounds__(256) void swish_fwd_kernel(const float* z, float* y, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += step) st4(y, i, swish4(ld4(z, i)));
+        if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+            const int64_t i = (n4 << 2) + threadIdx.x;
+            y[i] = swish_f(z[i]);
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += step) y[i] = swish_f(z[i]);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void swish_fwd_bf16_kernel(const bf16_t* z, bf16_t* y, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        const int64_t n8 = n >> 3;
+        for (int64_t i = tid; i < n8; i += step) {
+            f8 v = ld8(z, i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v.v[j] = swish_f(v.v[j]);
+            st8(y, i, v);
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
+            const int64_t i = (n8 << 3) + threadIdx.x;
+            y[i] = (bf16_t)bfbits(swish_f(bf1(z, i)));
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += step) y[i] = (bf16_t)bfbits(swish_f(bf1(z, i)));
+    }
+}
+
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ aux,
                                                       float* __restrict__ dz, int64_t n, int act) {
     const int64_t n4 = n >> 2;
@@ -631,13 +694,19 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
         const float4 d = reinterpret_cast<const float4*>(dy)[i], z = reinterpret_cast<const float4*>(aux)[i];
         float4 o;
         if (act == YTVLN_EPI_GELU) o = make_float4(d.x * dgelu_erf(z.x), d.y * dgelu_erf(z.y), d.z * dgelu_erf(z.z), d.w * dgelu_erf(z.w));
+        else if (act == YTVLN_ACT_SWISH) o = mul_dswish4(d, z);
         else o = make_float4(z.x > 0.f ? d.x : 0.f, z.y > 0.f ? d.y : 0.f, z.z > 0.f ? d.z : 0.f, z.w > 0.f ? d.w : 0.f);
         reinterpret_cast<float4*>(dz)[i] = o;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = (n4 << 2) + threadIdx.x;
-        dz[i] = act == YTVLN_EPI_GELU ? dy[i] * dgelu_erf(aux[i]) : (aux[i] > 0.f ? dy[i] : 0.f);
+        dz[i] = act == YTVLN_EPI_GELU ? dy[i] * dgelu_erf(aux[i]) : act == YTVLN_ACT_SWISH ? dy[i] * dswish_f(aux[i]) : (aux[i] > 0.f ? dy[i] : 0.f);
     }
+}
+
+// swish backward for fp32 pointers off the 16-byte grid (views into a larger buffer): one element per lane
+__global__ __launch_bounds__(256) void swish_bwd_scalar_kernel(const float* __restrict__ dy, const float* __restrict__ aux, float* __restrict__ dz, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dz[i] = dy[i] * dswish_f(aux[i]);
 }
 
 __global__ __launch_bounds__(256) void act_bwd_bf16_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ aux, bf16_t* __restrict__ dz, int64_t n4, int act) {
@@ -645,8 +714,32 @@ __global__ __launch_bounds__(256) void act_bwd_bf16_kernel(const bf16_t* __restr
         const float4 d = ld4(dy, i), z = ld4(aux, i);
         float4 o;
         if (act == YTVLN_EPI_GELU) o = make_float4(d.x * dgelu_erf(z.x), d.y * dgelu_erf(z.y), d.z * dgelu_erf(z.z), d.w * dgelu_erf(z.w));
+        else if (act == YTVLN_ACT_SWISH) o = mul_dswish4(d, z);
         else o = make_float4(z.x > 0.f ? d.x : 0.f, z.y > 0.f ? d.y : 0.f, z.z > 0.f ? d.z : 0.f, z.w > 0.f ? d.w : 0.f);
         st4(dz, i, o);
+    }
+}
+
+// The swish backward of the bf16-resident path: 16 bytes per lane when the pointers allow it (VEC), one element per lane for the tail and for
+// everything else -- the widths of the small heads are not all multiples of 4, which is what the gelu / relu form above asks for.
+template <bool VEC>
+__global__ __launch_bounds__(256) void swish_bwd_bf16_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ aux, bf16_t* __restrict__ dz, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        const int64_t n8 = n >> 3;
+        for (int64_t i = tid; i < n8; i += step) {
+            const f8 d = ld8(dy, i), z = ld8(aux, i);
+            f8 o;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.v[j] = d.v[j] * dswish_f(z.v[j]);
+            st8(dz, i, o);
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
+            const int64_t i = (n8 << 3) + threadIdx.x;
+            dz[i] = (bf16_t)bfbits(bf1(dy, i) * dswish_f(bf1(aux, i)));
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += step) dz[i] = (bf16_t)bfbits(bf1(dy, i) * dswish_f(bf1(aux, i)));
     }
 }
 
@@ -830,14 +923,33 @@ extern "C" int ytvln_gather_rows_f32(const float* x, int64_t ldx, const int64_t*
     return 0;
 }
 
+static inline unsigned ew_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(items, 256), 4096)); }
+
 extern "C" int ytvln_act_bwd_f32(const float* dy, const float* aux, float* dz, int64_t n, int act, void* stream) {
     YT_REQUIRE(dy && aux && dz, "act_bwd: null pointer");
-    YT_REQUIRE(act == YTVLN_EPI_GELU || act == YTVLN_EPI_RELU, "act_bwd: bad act %d", act);
-    YT_REQUIRE(al16(dy) && al16(aux) && al16(dz), "act_bwd: pointers must be 16-byte aligned");
+    YT_REQUIRE(act == YTVLN_EPI_GELU || act == YTVLN_EPI_RELU || act == YTVLN_ACT_SWISH, "act_bwd: bad act %d", act);
+    const bool aligned = al16(dy) && al16(aux) && al16(dz);
+    YT_REQUIRE(aligned || act == YTVLN_ACT_SWISH, "act_bwd: pointers must be 16-byte aligned");
+    YT_REQUIRE(n >= 0, "act_bwd: n < 0");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n / 4, 256), 4096))), dim3(256), 0,
-                       as_stream(stream), dy, aux, dz, n, act);
+    if (aligned)
+        hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream), dy, aux, dz, n, act);
+    else
+        hipLaunchKernelGGL(swish_bwd_scalar_kernel, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), dy, aux, dz, n);
     YT_LAUNCH_CHECK("act_bwd");
+    return 0;
+}
+
+extern "C" int ytvln_act_fwd_f32(const float* z, float* y, int64_t n, int act, void* stream) {
+    YT_REQUIRE(act == YTVLN_ACT_SWISH, "act_fwd: bad act %d (swish only: gelu and relu are GEMM epilogues)", act);
+    YT_REQUIRE(n >= 0, "act_fwd: n < 0");
+    if (n == 0) return 0;          // (an empty tensor has no address)
+    YT_REQUIRE(z && y, "act_fwd: null pointer");
+    if (al16(z) && al16(y))
+        hipLaunchKernelGGL(swish_fwd_kernel<true>, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream), z, y, n);
+    else
+        hipLaunchKernelGGL(swish_fwd_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), z, y, n);
+    YT_LAUNCH_CHECK("act_fwd");
     return 0;
 }
 
@@ -949,11 +1061,33 @@ extern "C" int ytvln_ln_bwd_bf16(const uint16_t* dy, const uint16_t* s, const fl
 
 extern "C" int ytvln_act_bwd_bf16(const uint16_t* dy, const uint16_t* aux, uint16_t* dz, int64_t n, int act, void* stream) {
     YT_REQUIRE(dy && aux && dz, "act_bwd_bf16: null pointer");
-    YT_REQUIRE(act == YTVLN_EPI_GELU || act == YTVLN_EPI_RELU, "act_bwd_bf16: bad act %d", act);
+    YT_REQUIRE(act == YTVLN_EPI_GELU || act == YTVLN_EPI_RELU || act == YTVLN_ACT_SWISH, "act_bwd_bf16: bad act %d", act);
+    hipStream_t st = as_stream(stream);
+    if (act == YTVLN_ACT_SWISH) {          // any n, any (2-byte) alignment
+        YT_REQUIRE(n >= 0, "act_bwd_bf16: n < 0");
+        if (n == 0) return 0;
+        if (al16(dy) && al16(aux) && al16(dz)) hipLaunchKernelGGL(swish_bwd_bf16_kernel<true>, dim3(ew_grid(n / 8)), dim3(256), 0, st, dy, aux, dz, n);
+        else hipLaunchKernelGGL(swish_bwd_bf16_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, st, dy, aux, dz, n);
+        YT_LAUNCH_CHECK("act_bwd_bf16");
+        return 0;
+    }
     YT_REQUIRE(al8(dy) && al8(aux) && al8(dz) && n % 4 == 0, "act_bwd_bf16: pointers must be 8-byte aligned and n a multiple of 4");
     if (n == 0) return 0;
     hipLaunchKernelGGL(act_bwd_bf16_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n / 4, 256), 4096))), dim3(256), 0,
-                       as_stream(stream), dy, aux, dz, n / 4, act);
+                       st, dy, aux, dz, n / 4, act);
     YT_LAUNCH_CHECK("act_bwd_bf16");
+    return 0;
+}
+
+extern "C" int ytvln_act_fwd_bf16(const uint16_t* z, uint16_t* y, int64_t n, int act, void* stream) {
+    YT_REQUIRE(act == YTVLN_ACT_SWISH, "act_fwd_bf16: bad act %d (swish only: gelu and relu are GEMM epilogues)", act);
+    YT_REQUIRE(n >= 0, "act_fwd_bf16: n < 0");
+    if (n == 0) return 0;
+    YT_REQUIRE(z && y, "act_fwd_bf16: null pointer");
+    if (al16(z) && al16(y))
+        hipLaunchKernelGGL(swish_fwd_bf16_kernel<true>, dim3(ew_grid(n / 8)), dim3(256), 0, as_stream(stream), z, y, n);
+    else
+        hipLaunchKernelGGL(swish_fwd_bf16_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), z, y, n);
+    YT_LAUNCH_CHECK("act_fwd_bf16");
     return 0;
 }

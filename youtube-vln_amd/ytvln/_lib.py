@@ -65,6 +65,7 @@ SIGNATURES = {
     "ytvln_text_embed_fwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I64, I32, I32, F32, F32, P, I64, P],
     "ytvln_image_embed_fwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],
     "ytvln_act_bwd_bf16": [P, P, P, I64, I32, P],
+    "ytvln_act_fwd_bf16": [P, P, I64, I32, P],
     "ytvln_ce_fwd_bf16": [P, I64, P, I64, P, P, P, I32, I32, P],
     "ytvln_ce_bwd_bf16": [P, I64, P, I64, P, P, P, P, I64, I32, I32, P],
     "ytvln_kl_fwd_bf16": [P, I64, P, I64, P, P, P, P, I32, I32, P],
@@ -78,6 +79,7 @@ SIGNATURES = {
     "ytvln_text_embed_fwd_f32": [P, P, P, P, P, P, P, P, P, P, P, I64, I32, I32, F32, F32, P, I64, P],
     "ytvln_image_embed_fwd_f32": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],
     "ytvln_act_bwd_f32": [P, P, P, I64, I32, P],
+    "ytvln_act_fwd_f32": [P, P, I64, I32, P],
     "ytvln_dropout_f32": [P, P, I64, F32, P, I64, P],
     "ytvln_attn_fwd_f32": [P, I64, P, I64, P, I64, P, P, I64, P, I32, I32, I32, I32, I32, F32, F32, P, I64, P],
     "ytvln_attn_bwd_f32": [P, I64, P, I64, P, I64, P, P, P, I64, P, P, P, I64, P, I64, P, I64, I32, I32, I32, I32, I32,
@@ -111,6 +113,7 @@ RED_SUM, RED_MAX, RED_MIN = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
 
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_MUL_DGELU, EPI_MUL_DRELU = 0, 1, 2, 3, 4
+ACT_SWISH = 5          # YTVLN_ACT_SWISH: the stand-alone activation kernels only (ytvln_act_fwd_*, ytvln_act_bwd_*), never a GEMM epilogue
 GEMM_A_ZERO_PADDED = 1
 GEMM_SPLIT_BF16X3 = 2
 ABI_VERSION = 2

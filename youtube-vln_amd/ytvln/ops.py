@@ -14,10 +14,11 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import EPI_GELU, EPI_MUL_DGELU, EPI_NONE, EPI_RELU, GEMM_A_ZERO_PADDED, GEMM_SPLIT_BF16X3, call
+from ._lib import ACT_SWISH, EPI_GELU, EPI_MUL_DGELU, EPI_NONE, EPI_RELU, GEMM_A_ZERO_PADDED, GEMM_SPLIT_BF16X3, call
 
 Tensor = torch.Tensor
-_ACT = {"none": EPI_NONE, None: EPI_NONE, "gelu": EPI_GELU, "relu": EPI_RELU}
+# "swish" is not a GEMM epilogue: the projection runs with EPI_NONE and ytvln_act_fwd_* follows (LinearFn / LinearBf16Fn)
+_ACT = {"none": EPI_NONE, None: EPI_NONE, "gelu": EPI_GELU, "relu": EPI_RELU, "swish": ACT_SWISH}
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -570,7 +571,8 @@ def _accumulate_target(dres, M: int, K: int, *live):
 
 
 class LinearFn(torch.autograd.Function):
-    """y = act(x W^T + b)  -- nn.Linear + optional erf-GELU / ReLU epilogue, all on the fp32 MFMA GEMM.
+    """y = act(x W^T + b)  -- nn.Linear + optional erf-GELU / ReLU epilogue, all on the fp32 MFMA GEMM; act = "swish" is the plain GEMM
+    followed by the elementwise kernel ytvln_act_fwd_f32 (unfused by design: one extra read and write of [M, N]).
 
     `passthrough=True` returns (y, x): the second output is x itself, to be used by the RESIDUAL connection that skips the sublayer this
     projection opens (vilbert.py:322-325, 365-368: `LayerNorm(dropout(dense(...)) + input_tensor)`).  The residual branch's gradient then
@@ -589,17 +591,23 @@ class LinearFn(torch.autograd.Function):
         assert weight.shape[1] == K, (weight.shape, K)
         need_grad = any(ctx.needs_input_grad)
         epi = _ACT[act]
-        if epi == EPI_NONE:
-            y, ldy = _alloc_rows(M, N, x.device)          # wide odd widths (logits) get a 32-float aligned leading dimension
+        if epi == ACT_SWISH:          # unfused: the plain GEMM writes the pre-activation z (kept for the backward), then y = z * sigmoid(z)
+            z, ldy = torch.empty((M, N), dtype=torch.float32, device=x.device), N
+            _gemm(x2, lda, 0, weight, weight.stride(0), 1, z, N, M, N, K, bias=bias)
+            y = torch.empty_like(z) if need_grad else z          # nothing to keep without a backward: in place
+            call("ytvln_act_fwd_f32", _ptr(z), _ptr(y), M * N, ACT_SWISH, _stream())
         else:
-            y, ldy = torch.empty((M, N), dtype=torch.float32, device=x.device), N
-        z = torch.empty_like(y) if (epi == EPI_GELU and need_grad) else None
-        _gemm(x2, lda, 0, weight, weight.stride(0), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
+            if epi == EPI_NONE:
+                y, ldy = _alloc_rows(M, N, x.device)          # wide odd widths (logits) get a 32-float aligned leading dimension
+            else:
+                y, ldy = torch.empty((M, N), dtype=torch.float32, device=x.device), N
+            z = torch.empty_like(y) if (epi == EPI_GELU and need_grad) else None
+            _gemm(x2, lda, 0, weight, weight.stride(0), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
         ctx.epi, ctx.dims, ctx.lda, ctx.has_bias = epi, (M, N, K), lda, bias is not None
         ctx.in_shape = x.shape
         ctx.targets = _targets_of(weight)
         ctx.btargets = _targets_of(bias) if bias is not None else None
-        ctx.save_for_backward(x2, weight, z if epi == EPI_GELU else (y if epi == EPI_RELU else None))
+        ctx.save_for_backward(x2, weight, z if epi in (EPI_GELU, ACT_SWISH) else (y if epi == EPI_RELU else None))
         out = _view_rows_as(y, ldy, tuple(x.shape[:-1]) + (N,))
         return (out, x) if ctx.passthrough else out
 
@@ -890,18 +898,26 @@ class LinearBf16Fn(torch.autograd.Function):
         wb = _bf16_weight(weight)
         need_grad = any(ctx.needs_input_grad)
         epi = _ACT[act]
-        if out_fp32:
-            y, ldy = _alloc_rows(M, N, x.device)
+        if epi == ACT_SWISH:          # unfused, as in LinearFn: z is bf16 like the gelu aux
+            z, ldy = torch.empty((M, N), dtype=_BF16, device=x.device), N
+            _gemm_bf16(x2, lda, 0, wb, K, 1, z, N, M, N, K, bias=bias)
+            y = torch.empty_like(z) if need_grad else z
+            call("ytvln_act_fwd_bf16", z.data_ptr(), y.data_ptr(), M * N, ACT_SWISH, _stream())
+            if out_fp32:
+                y = y.float()
         else:
-            y, ldy = torch.empty((M, N), dtype=_BF16, device=x.device), N
-        z = torch.empty((M, N), dtype=_BF16, device=x.device) if (epi == EPI_GELU and need_grad) else None
-        _gemm_bf16(x2, lda, 0, wb, K, 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
+            if out_fp32:
+                y, ldy = _alloc_rows(M, N, x.device)
+            else:
+                y, ldy = torch.empty((M, N), dtype=_BF16, device=x.device), N
+            z = torch.empty((M, N), dtype=_BF16, device=x.device) if (epi == EPI_GELU and need_grad) else None
+            _gemm_bf16(x2, lda, 0, wb, K, 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
         ctx.epi, ctx.dims, ctx.lda, ctx.has_bias = epi, (M, N, K), lda, bias is not None
         ctx.in_shape = x.shape
         ctx.targets = _targets_of(weight)
         ctx.btargets = _targets_of(bias) if bias is not None else None
         # the ReLU backward needs the sign of the OUTPUT: a bf16 copy of it when the output itself leaves as fp32
-        aux = z if epi == EPI_GELU else ((y if y.dtype == _BF16 else cast_bf16(y)) if (epi == EPI_RELU and need_grad) else None)
+        aux = z if epi in (EPI_GELU, ACT_SWISH) else ((y if y.dtype == _BF16 else cast_bf16(y)) if (epi == EPI_RELU and need_grad) else None)
         ctx.save_for_backward(x2, weight, aux)
         out = _view_rows_as(y, ldy, tuple(x.shape[:-1]) + (N,))
         return (out, x) if ctx.passthrough else out

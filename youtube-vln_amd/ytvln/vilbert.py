@@ -157,8 +157,9 @@ def load_tf_weights_in_bert(model, tf_checkpoint_path):
 
 
 def _act_name(act) -> str:
-    if not isinstance(act, str) or act not in ("gelu", "relu"):
-        raise NotImplementedError(f"activation {act!r}: the HIP path implements 'gelu' (erf form) and 'relu'")
+    if not isinstance(act, str) or act not in ("gelu", "relu", "swish"):
+        raise NotImplementedError(f"activation {act!r}: the HIP path implements the strings 'gelu' (erf form), 'relu' and 'swish' "
+                                  "(callables and other names are refused)")
     return act
 
 
