@@ -309,6 +309,41 @@ int ytvln_attn_fwd_bf16(const ytvln_attn_problem* a, const ytvln_attn_problem* b
 int ytvln_attn_bwd_bf16(const ytvln_attn_problem* a, const ytvln_attn_problem* b, int N, int heads, int d, float scale,
                         const int64_t* rng, void* stream);
 
+/* Per-score additive bias: what the reference adds to the scores beside the key mask -- BertBiAttention's co_attention_mask
+ * (vilbert.py:581-582 for the text-over-regions direction, read through `.permute(0,1,3,2)`, and :603-604 for regions over text) and any
+ * attention_mask that broadcasts against [N, heads, T, T] in BertSelfAttention / BertImageSelfAttention (:294-297, :423-427):
+ *     s[n,h,i,j] = fadd(fadd(fmul(q_i.k_j, scale), mask[n,j]), bias[n,h,i,j]),    bias[n,h,i,j] = ptr[n*stride_n + h*stride_h + i*stride_q + j*stride_k]
+ * fp32, strides in ELEMENTS: stride_h = 0 broadcasts over heads, stride_n = 0 over pairs, and a transposed view is read in place by swapping
+ * stride_q and stride_k (no copy).  Only 4-byte alignment of `ptr` is required.  The caller's contract: every element
+ * (n < N, h < heads, i < Tq, j < Tk) addressed through the strides lies inside the allocation -- the library cannot check an extent.
+ * Checked: stride_q and stride_k are non-negative and (Tq-1) stride_q + (Tk-1) stride_k < 2^31 (offsets inside a (pair, head) plane are
+ * 32-bit); stride_n and stride_h are 64-bit, may have either sign, and fall under the caller's contract alone.  Values
+ * are finite or -inf; a query row whose scores are ALL -inf is NaN in the reference and unspecified here.  The bias is a constant: no
+ * gradient with respect to it is computed.  A NULL record or a NULL `ptr` means "no bias", so one call serves a pair with one biased side;
+ * a launch in which no problem has a bias runs exactly the kernels of the entry points above.  Problems WITH a bias run the two-wave / wave-pair
+ * fp32 kernels (never the one-wave forms selected by ATTN_W1) -- decided per launch.  softmax, lse, dropout decisions: unchanged. */
+typedef struct ytvln_attn_bias {
+    const float* ptr;
+    int64_t stride_n, stride_h, stride_q, stride_k;
+} ytvln_attn_bias;
+/* sizeof(ytvln_attn_bias) as the LIBRARY was built (see ytvln_attn_problem_size) */
+int64_t ytvln_attn_bias_size(void);
+/* ytvln_attn_fwd_pair / ytvln_attn_bwd_pair (fp32) and ytvln_attn_fwd_bf16 / ytvln_attn_bwd_bf16 with a bias record next to each problem
+ * (replaces vilbert.py:577-582, :597-604 and the broadcast adds of :294-297, :423-427).  `b` may be NULL (one problem: self-attention) in all
+ * four; N, heads, d must be positive.  In the bf16 forms the bias stays fp32, like mask and lse. */
+int ytvln_attn_fwd_bias_f32(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                            const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream);
+int ytvln_attn_bwd_bias_f32(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                            const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream);
+int ytvln_attn_fwd_bias_bf16(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                             const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream);
+int ytvln_attn_bwd_bias_bf16(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                             const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream);
+/* ytvln_attn_probs_f32 with the bias added to the scores (vilbert.py:585, :607 with use_co_attention_mask: the probabilities the reference
+ * returns are the biased ones); `bias` NULL or bias->ptr NULL = ytvln_attn_probs_f32. */
+int ytvln_attn_probs_bias_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* mask, const ytvln_attn_bias* bias,
+                              const float* lse, float* probs, int N, int heads, int Tq, int Tk, int d, float scale, void* stream);
+
 /* probs[n,h,i,j] = exp(q_i.k_j*scale + mask - lse): the attention_probs tensor the reference returns when
  * output_all_attention_masks=True (vilbert.py:300, 311).  Diagnostic path, not on the training step. */
 int ytvln_attn_probs_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* mask, const float* lse,

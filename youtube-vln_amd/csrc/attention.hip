@@ -283,10 +283,14 @@ __device__ __forceinline__ void store_rows(const f32x16 (&acc)[DP / 32], float* 
 template <int DP, bool DROP>
 __device__ __forceinline__ void attn_fwd_dsplit_body(const AttnArgs& a, const int bx, const int h, const int n);      // below
 
-template <int DP, bool DROP>
-__device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int bx, const int h, const int n) {
+// BIAS: the workgroup's problem may carry a per-score bias (bs->ptr != NULL; one problem of a pair may have none).  Its 16 values of a score
+// block are plain global loads issued at the top of the tile, ahead of the LDS-DMA of V(t), and consumed after K.Q^T; the only counted waits of
+// this form are the vmcnt(0) in front of the barriers, so the compiler's own wait for them is all the bookkeeping there is.  BIAS = false is the
+// kernel as it was: every addition below is `if constexpr`.
+template <int DP, bool DROP, bool BIAS = false>
+__device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int bx, const int h, const int n, const ytvln_attn_bias* bs = nullptr) {
     constexpr int TS = 32 * DP, NJ = DP / 32;
-    if constexpr (DP == 128) {
+    if constexpr (DP == 128 && !BIAS) {
         // a two-wave workgroup holding a single query tile shares it between its waves (d-split form above); workgroup-uniform
         if (a.dsplit && blockDim.x == 128 && (bx * 2 + 1) * 32 >= a.Tq) {
             attn_fwd_dsplit_body<DP, DROP>(a, bx, h, n);
@@ -330,10 +334,26 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int bx, c
     uint32_t thr = 0; float ik = 1.f;
     const uint32_t dlo = (uint32_t)((((int64_t)n * a.heads + h) * a.Tq + qi));      // score row id; element = (row id, key)
     if (DROP) { key = make_drop_key(a.rng, a.site); thr = drop_threshold(a.p_drop); ik = 1.0f / (1.0f - a.p_drop); }
+    bool has_bias = false;
+    const float* __restrict__ bpl = nullptr;          // this (pair, head)'s plane of the bias; bfix: this lane's query row (a query past the end repeats the last one: not stored)
+    uint32_t bfix = 0; int bstr = 0;
+    if constexpr (BIAS) {
+        has_bias = bs->ptr != nullptr;
+        if (has_bias) { bpl = bias_plane(*bs, n, h); bfix = (uint32_t)(min(qi, a.Tq - 1) * (int)bs->stride_q); bstr = (int)bs->stride_k; }
+    }
 
     for (int t = 0; t < ntiles; ++t) {
         const int j0 = t * 32;
         TILE_WAIT_AND_SYNC();
+        float Bv[16];
+        if constexpr (BIAS) {
+            if (has_bias) bias_load16(Bv, bpl, bfix, bstr, j0, half, a.Tk);
+            else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Bv[r] = 0.f;
+            }
+            __builtin_amdgcn_sched_barrier(0);          // (ahead of the DMA: the wait for them then leaves V(t) in flight)
+        }
         Tile<DP>::issue(Vs, vb, ldv, j0, a.Tk, a.d, wave, nw, lane);
         if (active) {
             const f32x16 S = mma_rows<DP, 8>(Ks, Qr, lo);
@@ -344,6 +364,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int bx, c
                 P[4 * g] = score(S[4 * g], a.scale, mk.x); P[4 * g + 1] = score(S[4 * g + 1], a.scale, mk.y);
                 P[4 * g + 2] = score(S[4 * g + 2], a.scale, mk.z); P[4 * g + 3] = score(S[4 * g + 3], a.scale, mk.w);
             }
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) P[r] = __fadd_rn(P[r], Bv[r]);
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) mt = fmaxf(mt, P[r]);
             mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
@@ -353,7 +377,8 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int bx, c
             // per-query factor comes from the lane that owns that query (same half-wave) -- 16 ds_bpermute, a few times per kernel.
             if (__any(mt > m + RESCALE_THR)) {
                 const float mn = fmaxf(m, mt);
-                const float alpha = __expf(m - mn);
+                // (BIAS: a -inf bias can leave a query without a finite score for whole tiles -- m and mt both -inf; nothing to rescale)
+                const float alpha = (BIAS && mn == -INFINITY) ? 1.f : __expf(m - mn);
                 l *= alpha;
                 m = mn;
 #pragma unroll
@@ -364,8 +389,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, const int bx, c
                 }
             }
             float ps = 0.f;
+            const float mref = (BIAS && m == -INFINITY) ? 0.f : m;          // (exp(-inf - 0) = 0 where exp(-inf + inf) would be NaN)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { P[r] = __expf(P[r] - m); ps += P[r]; }
+            for (int r = 0; r < 16; ++r) { P[r] = __expf(P[r] - mref); ps += P[r]; }
             ps += __shfl_xor(ps, 32, 64);
             l += ps;
             if (DROP) {
@@ -547,8 +573,8 @@ __device__ __forceinline__ void attn_fwd_dsplit_body(const AttnArgs& a, const in
 // dQ.  LDS as in the forward.  Per key tile t:
 //     wait+barrier (V(t) landed, everyone finished dS.K(t-1)) -> DMA K(t)   | dP^T = V(t).dO^T
 //     wait+barrier (K(t) landed, everyone finished V(t).dO^T) -> DMA V(t+1) | S^T = K(t).Q^T, dS, dQ += dS.K(t)
-template <int DP, bool DROP>
-__device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx, const int h, const int n) {
+template <int DP, bool DROP, bool BIAS = false>
+__device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx, const int h, const int n, const ytvln_attn_bias* bs = nullptr) {
     constexpr int TS = 32 * DP, NJ = DP / 32;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;
@@ -601,6 +627,14 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
     const uint32_t dlo = (uint32_t)sidx;
     if (DROP) { key = make_drop_key(a.rng, a.site); thr = drop_threshold(a.p_drop); ik = 1.0f / (1.0f - a.p_drop); }
 
+    bool has_bias = false;          // (BIAS: see attn_fwd_body)
+    const float* __restrict__ bpl = nullptr;
+    uint32_t bfix = 0; int bstr = 0;
+    if constexpr (BIAS) {
+        has_bias = bs->ptr != nullptr;
+        if (has_bias) { bpl = bias_plane(*bs, n, h); bfix = (uint32_t)(min(qi, a.Tq - 1) * (int)bs->stride_q); bstr = (int)bs->stride_k; }
+    }
+
     f32x16 dP;
     for (int t = 0; t < ntiles; ++t) {
         const int j0 = t * 32;
@@ -608,6 +642,18 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
         Tile<DP>::issue(Ks, kb, ldk, j0, a.Tk, a.d, wave, nw, lane);
         if (active) dP = mma_rows<DP, YT_ATTN_BWD_PIPE>(Vs, Gr, lo);
         TILE_WAIT_AND_SYNC();
+        // (at d = 128 Gr, Qr, dQ, dP and S already fill 256 registers and the 16 values spill whichever way they are fetched -- at once, or in
+        //  groups of four pinned next to their use: 68-132 bytes of scratch, LABNOTES -- so the biased d = 128 kernel is built for ONE wave per
+        //  SIMD, 512 registers, like the one-wave kernels unbiased problems take: attn_bwd_dq_bias_kernel's launch bounds)
+        float Bv[16];
+        if constexpr (BIAS) {
+            if (has_bias) bias_load16(Bv, bpl, bfix, bstr, j0, half, a.Tk);
+            else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Bv[r] = 0.f;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (t + 1 < ntiles) Tile<DP>::issue(Vs, vb, ldv, j0 + 32, a.Tk, a.d, wave, nw, lane);
         if (active) {
             const f32x16 S = mma_rows<DP, YT_ATTN_BWD_PIPE>(Ks, Qr, lo);
@@ -619,7 +665,9 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int r = 4 * g + u;
-                    const float p = __expf(score(S[r], a.scale, mkv[u]) - lse);
+                    float sc = score(S[r], a.scale, mkv[u]);
+                    if constexpr (BIAS) sc = __fadd_rn(sc, Bv[r]);
+                    const float p = __expf(sc - lse);
                     float dp = dP[r];
                     if (DROP) dp = attn_drop_hash((uint32_t)(j0 + krow(r, half)), dlo, key) >= thr ? dp * ik : 0.f;
                     dS[r] = p * (dp - dl);
@@ -988,8 +1036,8 @@ __device__ __forceinline__ void attn_bwd_dq_w1_body(const AttnArgs& a, const int
 //     barrier
 //     S-wave: dV += (P o keep)^T . dO                      D-wave: dS = P o (dP o keep - delta), dK += dS^T . Q
 //     (STAGES = 1: barrier, DMA tile t+1)
-template <int DP, bool DROP, int STAGES>
-__device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int bx, const int h, const int n) {
+template <int DP, bool DROP, int STAGES, bool BIAS = false>
+__device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int bx, const int h, const int n, const ytvln_attn_bias* bs = nullptr) {
     constexpr int TS = 32 * DP, NJ = DP / 32;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
@@ -1038,9 +1086,26 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
     uint32_t thr = 0; float ik = 1.f;
     if (DROP) { key = make_drop_key(a.rng, a.site); thr = drop_threshold(a.p_drop); ik = 1.0f / (1.0f - a.p_drop); }
 
+    bool has_bias = false;          // (BIAS: see attn_fwd_body; here the KEY is on the lane and the queries run down the registers, S-wave only)
+    const float* __restrict__ bpl = nullptr;
+    uint32_t bfix = 0; int bstr = 0;
+    if constexpr (BIAS) {
+        has_bias = bs->ptr != nullptr && role == 0;
+        if (has_bias) { bpl = bias_plane(*bs, n, h); bfix = (uint32_t)(min(kj, a.Tk - 1) * (int)bs->stride_k); bstr = (int)bs->stride_q; }
+    }
+
     float W[16];                                // S-wave: P (then P o keep); D-wave: dP (then dS)
     for (int t = 0; t < nqt; ++t) {
         TILE_WAIT_AND_SYNC();
+        float Bv[16];
+        if constexpr (BIAS) {
+            if (has_bias) bias_load16(Bv, bpl, bfix, bstr, t * 32, half, a.Tq);
+            else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Bv[r] = 0.f;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (STAGES == 2 && t + 1 < nqt) issue(t + 1);
         const float* Qs = smem + (STAGES == 2 ? (t & 1) : 0) * 2 * TS;
         const float* Gs = Qs + TS;
@@ -1052,8 +1117,15 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const float4 ls = lds4(Lrow + i0 + 8 * g + 4 * half);
+                    if constexpr (BIAS) {
+                        W[4 * g] = __expf(__fadd_rn(score(S[4 * g], a.scale, mk), Bv[4 * g]) - ls.x);
+                        W[4 * g + 1] = __expf(__fadd_rn(score(S[4 * g + 1], a.scale, mk), Bv[4 * g + 1]) - ls.y);
+                        W[4 * g + 2] = __expf(__fadd_rn(score(S[4 * g + 2], a.scale, mk), Bv[4 * g + 2]) - ls.z);
+                        W[4 * g + 3] = __expf(__fadd_rn(score(S[4 * g + 3], a.scale, mk), Bv[4 * g + 3]) - ls.w);
+                    } else {
                     W[4 * g] = __expf(score(S[4 * g], a.scale, mk) - ls.x); W[4 * g + 1] = __expf(score(S[4 * g + 1], a.scale, mk) - ls.y);
                     W[4 * g + 2] = __expf(score(S[4 * g + 2], a.scale, mk) - ls.z); W[4 * g + 3] = __expf(score(S[4 * g + 3], a.scale, mk) - ls.w);
+                    }
                     *reinterpret_cast<float4*>(Xp + (g * 64 + lane) * 4) = make_float4(W[4 * g], W[4 * g + 1], W[4 * g + 2], W[4 * g + 3]);
                 }
             } else {
@@ -1203,10 +1275,10 @@ __device__ __forceinline__ void attn_bwd_dkv_w1_body(const AttnArgs& a, const in
 }
 
 // diagnostic: materialise attention_probs (reference returns them when output_all_attention_masks=True)
-__global__ __launch_bounds__(256) void attn_probs_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k,
-                                                         int64_t ldk, const float* __restrict__ mask, const float* __restrict__ lse,
-                                                         float* __restrict__ probs, int N, int heads, int Tq, int Tk, int d,
-                                                         float scale) {
+template <bool BIAS>
+__device__ __forceinline__ void attn_probs_body(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
+                                                const float* __restrict__ mask, const float* __restrict__ lse, float* __restrict__ probs, int N,
+                                                int heads, int Tq, int Tk, int d, float scale, const ytvln_attn_bias* bs) {
     const int64_t total = (int64_t)N * heads * Tq * Tk;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int j = (int)(i % Tk);
@@ -1218,8 +1290,22 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const float* __restrict
         const float* kp = k + (n * Tk + j) * ldk + h * d;
         float acc = 0.f;
         for (int c = 0; c < d; ++c) acc = fmaf(qp[c], kp[c], acc);
-        probs[i] = __expf(score(acc, scale, mask ? mask[n * Tk + j] : 0.f) - lse[(n * heads + h) * Tq + qi]);
+        float sc = score(acc, scale, mask ? mask[n * Tk + j] : 0.f);
+        if constexpr (BIAS) sc = __fadd_rn(sc, bs->ptr[n * bs->stride_n + h * bs->stride_h + qi * bs->stride_q + j * bs->stride_k]);
+        probs[i] = __expf(sc - lse[(n * heads + h) * Tq + qi]);
     }
+}
+__global__ __launch_bounds__(256) void attn_probs_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k,
+                                                         int64_t ldk, const float* __restrict__ mask, const float* __restrict__ lse,
+                                                         float* __restrict__ probs, int N, int heads, int Tq, int Tk, int d,
+                                                         float scale) {
+    attn_probs_body<false>(q, ldq, k, ldk, mask, lse, probs, N, heads, Tq, Tk, d, scale, nullptr);
+}
+__global__ __launch_bounds__(256) void attn_probs_bias_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k,
+                                                              int64_t ldk, const float* __restrict__ mask, const float* __restrict__ lse,
+                                                              float* __restrict__ probs, int N, int heads, int Tq, int Tk, int d,
+                                                              float scale, const ytvln_attn_bias bs) {
+    attn_probs_body<true>(q, ldq, k, ldk, mask, lse, probs, N, heads, Tq, Tk, d, scale, &bs);
 }
 
 // ---- kernel entry points: one launch covers ONE problem or the TWO directions of BertBiAttention (1-D grid: the first nb0
@@ -1227,6 +1313,8 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const float* __restrict
 // which stream the same K/V (or Q/dO) rows -- run on the same XCD and share its L2; with two problems in the launch the hardware
 // dispatcher fills the slots that one direction's last partial round would leave idle with the other direction's workgroups.
 struct AttnLaunch { AttnArgs p[2]; int nb0, gx0, gx1; };
+// a launch in which at least one problem carries a bias: the unbiased kernels never see this record (their argument block is AttnLaunch, as before)
+struct AttnLaunchB { AttnLaunch l; ytvln_attn_bias bias[2]; };
 
 #define YT_ATTN_DECODE(BODY_CALL)                                                                              \
     const int raw = blockIdx.x;                                                                                \
@@ -1251,6 +1339,24 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_w1_kernel(const AttnLaunch b)
 template <int DP, bool DROP, int STAGES>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnLaunch b) { YT_ATTN_DECODE((attn_bwd_dkv_body<DP, DROP, STAGES>(a, bx, h, n))); }
 #undef YT_ATTN_DECODE
+// the biased forms: the two-wave / wave-pair bodies only (the one-wave kernels sit at their register limit and keep the mask row in registers)
+#define YT_ATTN_DECODE_B(BODY_CALL)                                                                            \
+    const AttnLaunch& b = bb.l;                                                                                \
+    const int raw = blockIdx.x;                                                                                \
+    const int which = raw < b.nb0 ? 0 : 1;                                                                     \
+    const int bid = which ? xcd_remap(raw - b.nb0, (int)gridDim.x - b.nb0) : xcd_remap(raw, b.nb0);            \
+    const int gx = which ? b.gx1 : b.gx0;                                                                      \
+    const AttnArgs& a = b.p[which];                                                                            \
+    const ytvln_attn_bias* bs = &bb.bias[which];                                                               \
+    const int bx = bid % gx, h = (bid / gx) % a.heads, n = bid / (gx * a.heads);                               \
+    BODY_CALL
+template <int DP, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_fwd_bias_kernel(const AttnLaunchB bb) { YT_ATTN_DECODE_B((attn_fwd_body<DP, DROP, true>(a, bx, h, n, bs))); }
+template <int DP, bool DROP>
+__global__ __launch_bounds__(256, DP == 128 ? 1 : 2) void attn_bwd_dq_bias_kernel(const AttnLaunchB bb) { YT_ATTN_DECODE_B((attn_bwd_dq_body<DP, DROP, true>(a, bx, h, n, bs))); }
+template <int DP, bool DROP, int STAGES>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bias_kernel(const AttnLaunchB bb) { YT_ATTN_DECODE_B((attn_bwd_dkv_body<DP, DROP, STAGES, true>(a, bx, h, n, bs))); }
+#undef YT_ATTN_DECODE_B
 
 // Waves per workgroup of the forward / dQ kernels (32 queries each).  d > 64 (256-VGPR kernels, two waves per SIMD, 33 KB of LDS): two-wave
 // workgroups -- four of them fill a CU's eight wave slots, and a sequence of 9 query tiles costs one idle wave in five workgroups.  Smaller
@@ -1304,16 +1410,16 @@ static size_t lds_dkv(int dp, int stages, int npairs, int Tq) {
         else if ((dp_) == 64) YT_DISPATCH_DROP(KERNEL, 64, drop_, __VA_ARGS__);        \
         else YT_DISPATCH_DROP(KERNEL, 128, drop_, __VA_ARGS__);                        \
     } while (0)
-#define YT_DKV_DROP(ST, DPV, drop_, ...)                                               \
+#define YT_DKV_DROP(KERNEL, ST, DPV, drop_, ...)                                       \
     do {                                                                               \
-        if (drop_) hipLaunchKernelGGL((attn_bwd_dkv_kernel<DPV, true, ST>), __VA_ARGS__);   \
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<DPV, false, ST>), __VA_ARGS__);        \
+        if (drop_) hipLaunchKernelGGL((KERNEL<DPV, true, ST>), __VA_ARGS__);           \
+        else hipLaunchKernelGGL((KERNEL<DPV, false, ST>), __VA_ARGS__);                \
     } while (0)
-#define YT_DKV_DP(ST, dp_, drop_, ...)                                                 \
+#define YT_DKV_DP(KERNEL, ST, dp_, drop_, ...)                                         \
     do {                                                                               \
-        if ((dp_) == 32) YT_DKV_DROP(ST, 32, drop_, __VA_ARGS__);                      \
-        else if ((dp_) == 64) YT_DKV_DROP(ST, 64, drop_, __VA_ARGS__);                 \
-        else YT_DKV_DROP(ST, 128, drop_, __VA_ARGS__);                                 \
+        if ((dp_) == 32) YT_DKV_DROP(KERNEL, ST, 32, drop_, __VA_ARGS__);              \
+        else if ((dp_) == 64) YT_DKV_DROP(KERNEL, ST, 64, drop_, __VA_ARGS__);         \
+        else YT_DKV_DROP(KERNEL, ST, 128, drop_, __VA_ARGS__);                         \
     } while (0)
 
 }  // namespace ytvln
@@ -1321,8 +1427,29 @@ static size_t lds_dkv(int dp, int stages, int npairs, int Tq) {
 using namespace ytvln;
 
 // ---- launches over one or two problems of equal (N, heads, d) ------------------------------------------------------------------
-static int launch_fwd(AttnLaunch& b, int np, hipStream_t s) {
-    if (np > 1 && b.p[1].Tk > b.p[0].Tk) std::swap(b.p[0], b.p[1]);          // forward workgroups walk key tiles: the long-key direction first (see launch_bwd)
+// a bias record as the kernels want it: NULL record -> ptr = NULL (no bias)
+int ytvln::check_bias(const char* who, const ytvln_attn_bias& b, int Tq, int Tk) {
+    YT_REQUIRE(((uintptr_t)b.ptr & 3) == 0, "%s: bias must be 4-byte aligned", who);
+    YT_REQUIRE(b.stride_q >= 0 && b.stride_k >= 0, "%s: bias stride_q / stride_k must be non-negative", who);
+    YT_REQUIRE((int64_t)(Tq - 1) * b.stride_q + (int64_t)(Tk - 1) * b.stride_k < (1ll << 31),
+               "%s: a (pair, head) plane of the bias must span fewer than 2^31 elements", who);
+    return 0;
+}
+static int set_bias(const char* who, ytvln_attn_bias& dst, const ytvln_attn_bias* src, int Tq, int Tk) {
+    dst = ytvln_attn_bias{};
+    if (src && src->ptr) {
+        if (int rc = check_bias(who, *src, Tq, Tk)) return rc;
+        dst = *src;
+    }
+    return 0;
+}
+static void swap_problems(AttnLaunchB& bb) { std::swap(bb.l.p[0], bb.l.p[1]); std::swap(bb.bias[0], bb.bias[1]); }
+
+static int launch_fwd(AttnLaunchB& bb, int np, hipStream_t s) {
+    AttnLaunch& b = bb.l;
+    if (np > 1 && b.p[1].Tk > b.p[0].Tk) swap_problems(bb);          // forward workgroups walk key tiles: the long-key direction first (see launch_bwd)
+    // decided per launch: a problem with a bias takes the two-wave form (and its partner in a pair launch with it)
+    const bool biased = bb.bias[0].ptr || (np > 1 && bb.bias[1].ptr);
     const AttnArgs& a0 = b.p[0];
     const int dp = dp_of(a0.d);
     bool drop = false;
@@ -1335,7 +1462,7 @@ static int launch_fwd(AttnLaunch& b, int np, hipStream_t s) {
     }
     // one wave per workgroup and per SIMD (attn_fwd_w1_body); option ATTN_W1 bit 0 clear: the two-wave form everywhere
     const bool w1_dim = a0.d == 128 || a0.d == 64;             // unpadded heads the one-wave kernels are instantiated for
-    if ((opt(OPT_ATTN_W1) & 1) && w1_dim && maxTk <= 512) {
+    if (!biased && (opt(OPT_ATTN_W1) & 1) && w1_dim && maxTk <= 512) {
         b.gx0 = (int)cdiv(b.p[0].Tq, 32);
         b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tq, 32) : 1;
         b.nb0 = b.gx0 * a0.heads * a0.N;
@@ -1362,15 +1489,18 @@ static int launch_fwd(AttnLaunch& b, int np, hipStream_t s) {
     b.nb0 = b.gx0 * a0.heads * a0.N;
     const int64_t total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
     YT_REQUIRE(total < (1ll << 31), "attn_fwd: grid too large");
-    const bool dsplit = opt(OPT_ATTN_DSPLIT) && dp == 128 && nw == 2;
+    const bool dsplit = !biased && opt(OPT_ATTN_DSPLIT) && dp == 128 && nw == 2;
     for (int i = 0; i < np; ++i) b.p[i].dsplit = dsplit;
     const size_t lds_bytes = lds_fwd(dp, maxTk) + (dsplit ? 4096 : 0);
-    YT_DISPATCH(attn_fwd_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_bytes, s, b);
+    if (biased) YT_DISPATCH(attn_fwd_bias_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_bytes, s, bb);
+    else YT_DISPATCH(attn_fwd_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_bytes, s, b);
     YT_LAUNCH_CHECK("attn_fwd");
     return 0;
 }
 
-static int launch_bwd(AttnLaunch& b, int np, hipStream_t s) {
+static int launch_bwd(AttnLaunchB& bb, int np, hipStream_t s) {
+    AttnLaunch& b = bb.l;
+    const bool biased = bb.bias[0].ptr || (np > 1 && bb.bias[1].ptr);          // (per launch, see launch_fwd)
     const AttnArgs& a0 = b.p[0];
     const int dp = dp_of(a0.d);
     bool drop = false;
@@ -1387,10 +1517,10 @@ static int launch_bwd(AttnLaunch& b, int np, hipStream_t s) {
     // delta[n,h,q] = sum_c dctx.ctx is produced by the dQ kernel's prologue (it owns the query rows) and read by the dK/dV kernel that
     // follows it on the stream
     for (int i = 0; i < np; ++i) b.p[i].delta_out = const_cast<float*>(b.p[i].delta);
-    if (np > 1 && b.p[1].Tk > b.p[0].Tk) std::swap(b.p[0], b.p[1]);          // dQ workgroups walk key tiles: the long-key direction first
+    if (np > 1 && b.p[1].Tk > b.p[0].Tk) swap_problems(bb);          // dQ workgroups walk key tiles: the long-key direction first
     {
         // one wave per workgroup and per SIMD (attn_bwd_dq_w1_body); option ATTN_W1 bit 1 clear: the two-wave form
-        const bool w1 = (opt(OPT_ATTN_W1) & 2) && (a0.d == 128 || a0.d == 64) && maxTk <= 512;      // (unpadded heads, mask row in registers)
+        const bool w1 = !biased && (opt(OPT_ATTN_W1) & 2) && (a0.d == 128 || a0.d == 64) && maxTk <= 512;      // (unpadded heads, mask row in registers)
         const int nw = w1 ? 1 : pick_waves(maxTq, a0.d);
         b.gx0 = (int)cdiv(b.p[0].Tq, 32 * nw);
         b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tq, 32 * nw) : 1;
@@ -1398,6 +1528,7 @@ static int launch_bwd(AttnLaunch& b, int np, hipStream_t s) {
         const int64_t total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
         YT_REQUIRE(total < (1ll << 31), "attn_bwd: grid too large");
         if (w1) YT_W1(attn_bwd_dq_w1_kernel, lds_fwd(dp, maxTk));
+        else if (biased) YT_DISPATCH(attn_bwd_dq_bias_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_fwd(dp, maxTk), s, bb);
         else YT_DISPATCH(attn_bwd_dq_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_fwd(dp, maxTk), s, b);
     }
     // one wave per workgroup and per SIMD (attn_bwd_dkv_w1_body; option ATTN_W1 bit 2 clear: always the wave-pair form): unpadded fp32 heads, lse /
@@ -1407,11 +1538,11 @@ static int launch_bwd(AttnLaunch& b, int np, hipStream_t s) {
     // has the longer workgroups; those go first (the grid is handed out in order: long ones last would leave a tail of a few hundred long
     // workgroups on a mostly idle chip -- 288-query x 80-key workgroups behind 80 x 288 ones: ~30 instead of ~24 tile times).  The forward / dQ
     // launches walk KEY tiles; BertBiAttention already passes its long-key direction first.
-    if (np > 1 && b.p[1].Tq > b.p[0].Tq) std::swap(b.p[0], b.p[1]);
+    if (np > 1 && b.p[1].Tq > b.p[0].Tq) swap_problems(bb);
     const int64_t w1_waves = (cdiv(b.p[0].Tk, 32) + (np > 1 ? cdiv(b.p[1].Tk, 32) : 0)) * a0.heads * a0.N;
     const int64_t w1_slots = a0.d == 128 ? 1024 : 2048;          // (d = 64: 17 KB of LDS and < 256 registers per wave -> two per SIMD)
     const bool w1_fill = w1_waves * 100 >= cdiv(w1_waves, w1_slots) * w1_slots * 85;      // the last round at least ~85 % useful overall
-    if ((opt(OPT_ATTN_W1) & 4) && (a0.d == 128 || a0.d == 64) && maxTq <= 512 && (w1_fill || opt(OPT_ATTN_W1_DKV_ANY))) {
+    if (!biased && (opt(OPT_ATTN_W1) & 4) && (a0.d == 128 || a0.d == 64) && maxTq <= 512 && (w1_fill || opt(OPT_ATTN_W1_DKV_ANY))) {
         b.gx0 = (int)cdiv(b.p[0].Tk, 32);
         b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tk, 32) : 1;
         b.nb0 = b.gx0 * a0.heads * a0.N;
@@ -1428,8 +1559,11 @@ static int launch_bwd(AttnLaunch& b, int np, hipStream_t s) {
         const int64_t total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
         YT_REQUIRE(total < (1ll << 31), "attn_bwd: grid too large");
         const size_t lds = lds_dkv(dp, stages, npairs, maxTq);
-        if (stages == 1) YT_DKV_DP(1, dp, drop, dim3((unsigned)total), dim3(128 * npairs), lds, s, b);
-        else YT_DKV_DP(2, dp, drop, dim3((unsigned)total), dim3(128 * npairs), lds, s, b);
+        if (biased) {
+            if (stages == 1) YT_DKV_DP(attn_bwd_dkv_bias_kernel, 1, dp, drop, dim3((unsigned)total), dim3(128 * npairs), lds, s, bb);
+            else YT_DKV_DP(attn_bwd_dkv_bias_kernel, 2, dp, drop, dim3((unsigned)total), dim3(128 * npairs), lds, s, bb);
+        } else if (stages == 1) YT_DKV_DP(attn_bwd_dkv_kernel, 1, dp, drop, dim3((unsigned)total), dim3(128 * npairs), lds, s, b);
+        else YT_DKV_DP(attn_bwd_dkv_kernel, 2, dp, drop, dim3((unsigned)total), dim3(128 * npairs), lds, s, b);
     }
     YT_LAUNCH_CHECK("attn_bwd");
     return 0;
@@ -1438,8 +1572,8 @@ static int launch_bwd(AttnLaunch& b, int np, hipStream_t s) {
 extern "C" int ytvln_attn_fwd_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                                   const float* mask, float* ctx, int64_t ldo, float* lse, int N, int heads, int Tq, int Tk,
                                   int d, float scale, float p_drop, const int64_t* rng, int64_t site, void* stream) {
-    AttnLaunch b = {};
-    AttnArgs& a = b.p[0];
+    AttnLaunchB b = {};
+    AttnArgs& a = b.l.p[0];
     a.q = q; a.k = k; a.v = v; a.mask = mask; a.out = ctx; a.lse_out = lse;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.N = N; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = scale; a.p_drop = p_drop; a.rng = rng; a.site = site;
@@ -1451,8 +1585,8 @@ extern "C" int ytvln_attn_bwd_f32(const float* q, int64_t ldq, const float* k, i
                                   float* delta, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv,
                                   int N, int heads, int Tq, int Tk, int d, float scale, float p_drop, const int64_t* rng,
                                   int64_t site, void* stream) {
-    AttnLaunch b = {};
-    AttnArgs& a = b.p[0];
+    AttnLaunchB b = {};
+    AttnArgs& a = b.l.p[0];
     a.q = q; a.k = k; a.v = v; a.mask = mask; a.ctx = ctx; a.dctx = dctx; a.lse = lse; a.delta = delta;
     a.dq = dq; a.dk = dk; a.dv = dv;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
@@ -1473,18 +1607,18 @@ static void fill_args(AttnArgs& a, const ytvln_attn_problem& pr, int N, int head
 extern "C" int ytvln_attn_fwd_pair(const ytvln_attn_problem* pa, const ytvln_attn_problem* pb, int N, int heads, int d, float scale,
                                    const int64_t* rng, void* stream) {
     YT_REQUIRE(pa && pb, "attn_fwd_pair: null problem");
-    AttnLaunch b = {};
-    fill_args(b.p[0], *pa, N, heads, d, scale, rng);
-    fill_args(b.p[1], *pb, N, heads, d, scale, rng);
+    AttnLaunchB b = {};
+    fill_args(b.l.p[0], *pa, N, heads, d, scale, rng);
+    fill_args(b.l.p[1], *pb, N, heads, d, scale, rng);
     return launch_fwd(b, 2, as_stream(stream));
 }
 
 extern "C" int ytvln_attn_bwd_pair(const ytvln_attn_problem* pa, const ytvln_attn_problem* pb, int N, int heads, int d, float scale,
                                    const int64_t* rng, void* stream) {
     YT_REQUIRE(pa && pb, "attn_bwd_pair: null problem");
-    AttnLaunch b = {};
-    fill_args(b.p[0], *pa, N, heads, d, scale, rng);
-    fill_args(b.p[1], *pb, N, heads, d, scale, rng);
+    AttnLaunchB b = {};
+    fill_args(b.l.p[0], *pa, N, heads, d, scale, rng);
+    fill_args(b.l.p[1], *pb, N, heads, d, scale, rng);
     return launch_bwd(b, 2, as_stream(stream));
 }
 
@@ -1498,3 +1632,45 @@ extern "C" int ytvln_attn_probs_f32(const float* q, int64_t ldq, const float* k,
     YT_LAUNCH_CHECK("attn_probs");
     return 0;
 }
+
+// ---- the same launches with a per-score additive bias next to each problem (include/ytvln.h: ytvln_attn_bias) ---------------------------------
+static int bias_launch(bool backward, const char* who, const ytvln_attn_problem* pa, const ytvln_attn_bias* ba, const ytvln_attn_problem* pb,
+                       const ytvln_attn_bias* bbias, int N, int heads, int d, float scale, const int64_t* rng, void* stream) {
+    YT_REQUIRE(pa, "%s: null problem", who);
+    YT_REQUIRE(N > 0 && heads > 0 && d > 0, "%s: N, heads and d must be positive", who);
+    YT_REQUIRE(pa->Tq > 0 && pa->Tk > 0 && (!pb || (pb->Tq > 0 && pb->Tk > 0)), "%s: sequence lengths must be positive", who);
+    AttnLaunchB b = {};
+    fill_args(b.l.p[0], *pa, N, heads, d, scale, rng);
+    if (int rc = set_bias(who, b.bias[0], ba, pa->Tq, pa->Tk)) return rc;
+    if (pb) {
+        fill_args(b.l.p[1], *pb, N, heads, d, scale, rng);
+        if (int rc = set_bias(who, b.bias[1], bbias, pb->Tq, pb->Tk)) return rc;
+    }
+    return backward ? launch_bwd(b, pb ? 2 : 1, as_stream(stream)) : launch_fwd(b, pb ? 2 : 1, as_stream(stream));
+}
+
+extern "C" int ytvln_attn_fwd_bias_f32(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                                       const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream) {
+    return bias_launch(false, "attn_fwd_bias_f32", a, bias_a, b, bias_b, N, heads, d, scale, rng, stream);
+}
+
+extern "C" int ytvln_attn_bwd_bias_f32(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                                       const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream) {
+    return bias_launch(true, "attn_bwd_bias_f32", a, bias_a, b, bias_b, N, heads, d, scale, rng, stream);
+}
+
+extern "C" int ytvln_attn_probs_bias_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* mask, const ytvln_attn_bias* bias,
+                                         const float* lse, float* probs, int N, int heads, int Tq, int Tk, int d, float scale, void* stream) {
+    if (!bias || !bias->ptr) return ytvln_attn_probs_f32(q, ldq, k, ldk, mask, lse, probs, N, heads, Tq, Tk, d, scale, stream);
+    YT_REQUIRE(q && k && lse && probs, "attn_probs_bias: null pointer");
+    YT_REQUIRE(N > 0 && heads > 0 && Tq > 0 && Tk > 0 && d > 0, "attn_probs_bias: N, heads, Tq, Tk and d must be positive");
+    if (int rc = check_bias("attn_probs_bias", *bias, Tq, Tk)) return rc;
+    const int64_t total = (int64_t)N * heads * Tq * Tk;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(attn_probs_bias_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 8192)), dim3(256), 0, as_stream(stream), q, ldq,
+                       k, ldk, mask, lse, probs, N, heads, Tq, Tk, d, scale, *bias);
+    YT_LAUNCH_CHECK("attn_probs_bias");
+    return 0;
+}
+
+extern "C" int64_t ytvln_attn_bias_size(void) { return (int64_t)sizeof(ytvln_attn_bias); }

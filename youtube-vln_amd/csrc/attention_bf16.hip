@@ -47,6 +47,8 @@ struct BAttnArgs {
     uint64_t* keep;              // dropout keep decisions of the forward: [N * heads][query block][key tile][16] 64-bit lane masks (see battn_fwd_body)
 };
 struct BAttnLaunch { BAttnArgs p[2]; int nb0, gx0, gx1; };
+// a launch in which at least one problem carries a per-score bias (common.h: bias_load16); the unbiased kernels keep BAttnLaunch as their argument block
+struct BAttnLaunchB { BAttnLaunch l; ytvln_attn_bias bias[2]; };
 
 #define MFMA_B(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 #define B_RESCALE_THR 12.0f
@@ -191,8 +193,12 @@ __device__ __forceinline__ float b_halves_sum(float x) {
 //     wait K(t)   S^T = K(t).Q^T          -> DMA K(t+1)
 //     softmax (online, lazily moved reference), dropout, P -> bf16
 //     wait V(t)   O^T += V(t)^T.P^T       -> DMA V(t+1)
-template <int DP, bool DROP>
-__device__ __forceinline__ void battn_fwd_body(const BAttnArgs& a, const int bx, const int h, const int n) {
+// BIAS (all three kernels): the 16 bias values of a score block are plain global loads issued at the TOP of the tile, behind the two tiles that are
+// in flight, so the counted wait for the first of them allows 16 more operations when the problem has a bias (one problem of a pair may have
+// none: a wave-uniform branch); every later wait of the tile already covers them (vector memory retires in order).  BIAS = false is the kernel
+// as it was.
+template <int DP, bool DROP, bool BIAS = false>
+__device__ __forceinline__ void battn_fwd_body(const BAttnArgs& a, const int bx, const int h, const int n, const ytvln_attn_bias* bs = nullptr) {
     using T = BTile<DP>;
     constexpr int NS = DP / 16, NC = DP / 32, PC = T::PC;
     extern __shared__ __attribute__((aligned(16))) char bsmem[];
@@ -229,13 +235,28 @@ __device__ __forceinline__ void battn_fwd_body(const BAttnArgs& a, const int bx,
         for (int r = 0; r < 16; ++r) O[c][r] = 0.f;
     float m = -INFINITY, l = 0.f;
     const uint32_t dlo = (uint32_t)((((int64_t)n * a.heads + h) * a.Tq + qi));
+    bool has_bias = false;
+    const float* __restrict__ bpl = nullptr;          // this (pair, head)'s plane of the bias; bfix: this lane's query row
+    uint32_t bfix = 0; int bstr = 0;
+    if constexpr (BIAS) {
+        has_bias = bs->ptr != nullptr;
+        if (has_bias) { bpl = bias_plane(*bs, n, h); bfix = (uint32_t)(min(qi, a.Tq - 1) * (int)bs->stride_q); bstr = (int)bs->stride_k; }
+    }
     // (a launch with dropout in either of its problems carries a keep buffer for both: the host checks it)
     uint64_t* const kblock = DROP ? a.keep + (((int64_t)n * a.heads + h) * ((a.Tq + 31) >> 5) + bx) * ntiles * 16 : nullptr;
 
     auto tile = [&](auto FIRST_T, auto MORE_T, const int t) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(FIRST_T)::value, more = decltype(MORE_T)::value;
         const int j0 = t * 32;
+        float Bv[16];
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Bv[r] = 0.f;
+            if (has_bias) bias_load16(Bv, bpl, bfix, bstr, j0, half, a.Tk);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (FIRST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // K(0), V(0), Q
+        else if (BIAS && has_bias) b_wait<PC + 16>();                       // K(t); V(t) and the bias values may still be on their way
         else b_wait<PC>();                                                  // K(t); V(t) may still be on its way
         f32x16 S;
 #pragma unroll
@@ -252,12 +273,16 @@ __device__ __forceinline__ void battn_fwd_body(const BAttnArgs& a, const int bx,
             P[4 * g] = bscore(S[4 * g], a.scale, mk.x); P[4 * g + 1] = bscore(S[4 * g + 1], a.scale, mk.y);
             P[4 * g + 2] = bscore(S[4 * g + 2], a.scale, mk.z); P[4 * g + 3] = bscore(S[4 * g + 3], a.scale, mk.w);
         }
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) P[r] = __fadd_rn(P[r], Bv[r]);
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) mt = fmaxf(mt, P[r]);
         mt = b_halves_max(mt);
         if (__any(mt > m + B_RESCALE_THR)) {          // lazily moved softmax reference: O and l are rescaled only when a row maximum grew by > THR
             const float mn = fmaxf(m, mt);
-            const float alpha = __expf(m - mn);
+            const float alpha = (BIAS && mn == -INFINITY) ? 1.f : __expf(m - mn);          // (BIAS: see attn_fwd_body in attention.hip)
             l *= alpha;
             m = mn;
 #pragma unroll
@@ -266,8 +291,9 @@ __device__ __forceinline__ void battn_fwd_body(const BAttnArgs& a, const int bx,
                 for (int r = 0; r < 16; ++r) O[c][r] *= alpha;          // (the query is on the lane: a lane-local scalar)
         }
         float ps = 0.f;
+        const float mref = (BIAS && m == -INFINITY) ? 0.f : m;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { P[r] = __expf(P[r] - m); ps += P[r]; }
+        for (int r = 0; r < 16; ++r) { P[r] = __expf(P[r] - mref); ps += P[r]; }
         l += b_halves_sum(ps);
         if (DROP) {
             uint32_t mlo = 0, mhi = 0;          // lane r (< 16) collects mask r
@@ -310,8 +336,8 @@ __device__ __forceinline__ void battn_fwd_body(const BAttnArgs& a, const int bx,
 // LDS as the forward.  Prologue: delta[q] = sum_d dO.O (also written out for the dK/dV kernel).  Per key tile t:
 //     wait V(t)   dP^T = V(t).dO^T        -> DMA V(t+1)
 //     wait K(t)   S^T = K(t).Q^T;  p = exp(s - lse), dS = p o (dP o keep - delta);  dQ^T += K(t)^T.dS^T   -> DMA K(t+1)
-template <int DP, bool DROP>
-__device__ __forceinline__ void battn_bwd_dq_body(const BAttnArgs& a, const int bx, const int h, const int n) {
+template <int DP, bool DROP, bool BIAS = false>
+__device__ __forceinline__ void battn_bwd_dq_body(const BAttnArgs& a, const int bx, const int h, const int n, const ytvln_attn_bias* bs = nullptr) {
     using T = BTile<DP>;
     constexpr int NS = DP / 16, NC = DP / 32, PC = T::PC;
     extern __shared__ __attribute__((aligned(16))) char bsmem[];
@@ -362,6 +388,13 @@ __device__ __forceinline__ void battn_bwd_dq_body(const BAttnArgs& a, const int 
         for (int r = 0; r < 16; ++r) dQ[c][r] = 0.f;
     const uint64_t* const kblock = DROP ? a.keep + (((int64_t)n * a.heads + h) * ((a.Tq + 31) >> 5) + bx) * ntiles * 16 : nullptr;
     typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+    bool has_bias = false;
+    const float* __restrict__ bpl = nullptr;
+    uint32_t bfix = 0; int bstr = 0;
+    if constexpr (BIAS) {
+        has_bias = bs->ptr != nullptr;
+        if (has_bias) { bpl = bias_plane(*bs, n, h); bfix = (uint32_t)(min(qi, a.Tq - 1) * (int)bs->stride_q); bstr = (int)bs->stride_k; }
+    }
 
     auto tile = [&](auto FIRST_T, auto MORE_T, const int t) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(FIRST_T)::value, more = decltype(MORE_T)::value;
@@ -371,8 +404,16 @@ __device__ __forceinline__ void battn_bwd_dq_body(const BAttnArgs& a, const int 
             const uint64_t* kp = scalar_ptr(kblock + (int64_t)t * 16);          // (wave-uniform; s_nop: a scalar the VALU has just written needs wait states before SMEM reads it)
             asm volatile("s_nop 4\n\ts_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40" : "=&s"(ma), "=&s"(mb) : "s"(kp) : "memory");
         }
+        float Bv[16];
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Bv[r] = 0.f;
+            if (has_bias) bias_load16(Bv, bpl, bfix, bstr, j0, half, a.Tk);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // V(t); K(t) may still be on its way (first tile: the prologue's last loads have been consumed, so everything has landed)
         if (FIRST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (BIAS && has_bias) b_wait<PC + 16>();
         else b_wait<PC>();
         f32x16 dP;
 #pragma unroll
@@ -398,7 +439,9 @@ __device__ __forceinline__ void battn_bwd_dq_body(const BAttnArgs& a, const int 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int r = 4 * g + u;
-                const float p = __expf(bscore(S[r], a.scale, mkv[u]) - lse);
+                float sc = bscore(S[r], a.scale, mkv[u]);
+                if constexpr (BIAS) sc = __fadd_rn(sc, Bv[r]);
+                const float p = __expf(sc - lse);
                 float dp = dP[r];
                 if (DROP) {          // dp = keep ? dp / (1 - p_drop) : 0 -- the mask of register r is the select operand itself
                     const uint64_t m = r < 8 ? ((uint64_t)ma[2 * (r & 7) + 1] << 32) | ma[2 * (r & 7)] : ((uint64_t)mb[2 * (r & 7) + 1] << 32) | mb[2 * (r & 7)];
@@ -435,8 +478,8 @@ __device__ __forceinline__ void battn_bwd_dq_body(const BAttnArgs& a, const int 
 // The two halves recompute S (and share nothing else: dV needs P, dK needs dS = P o (dP - delta)), 40 instead of 32 matrix instructions per
 // tile, but each fits 256 registers, so TWO waves share a SIMD and one wave's ~200-390 vector instructions per tile run under the other's matrix
 // instructions -- the one-pass kernel serialises them (4100 cycles per tile against 1024 of matrix time, profiles/round6 notes in LABNOTES).
-template <int DP, bool DROP, int PART = 0>
-__device__ __forceinline__ void battn_bwd_dkv_body(const BAttnArgs& a, const int bx, const int h, const int n) {
+template <int DP, bool DROP, int PART = 0, bool BIAS = false>
+__device__ __forceinline__ void battn_bwd_dkv_body(const BAttnArgs& a, const int bx, const int h, const int n, const ytvln_attn_bias* bs = nullptr) {
     constexpr bool WANT_V = PART != 2, WANT_K = PART != 1;
     using T = BTile<DP>;
     constexpr int NS = DP / 16, NC = DP / 32, PC = T::PC;
@@ -485,6 +528,13 @@ __device__ __forceinline__ void battn_bwd_dkv_body(const BAttnArgs& a, const int
     // keep bits (see the header): this lane's key is column c = l31 of the block; in the forward's layout that key sat in register rf of half hf
     const int kc = l31, hf = (kc >> 2) & 1, rf = (kc & 3) + 4 * (kc >> 3);
     const int nkt = (a.Tk + 31) >> 5;
+    bool has_bias = false;          // (the KEY is on the lane here, the queries run down the registers)
+    const float* __restrict__ bpl = nullptr;
+    uint32_t bfix = 0; int bstr = 0;
+    if constexpr (BIAS) {
+        has_bias = bs->ptr != nullptr;
+        if (has_bias) { bpl = bias_plane(*bs, n, h); bfix = (uint32_t)(min(kj, a.Tk - 1) * (int)bs->stride_k); bstr = (int)bs->stride_q; }
+    }
     const uint64_t* const kcol = DROP ? a.keep + ((((int64_t)n * a.heads + h) * nqt) * nkt + bx) * 16 + rf : nullptr;
 
     auto tile = [&](auto MORE_T, const int t) __attribute__((always_inline)) {
@@ -495,6 +545,15 @@ __device__ __forceinline__ void battn_bwd_dkv_body(const BAttnArgs& a, const int
             const uint64_t mk64 = kcol[(int64_t)t * nkt * 16];
             kw = (uint32_t)(hf ? (mk64 >> 32) : mk64) >> (4 * half);
         }
+        float Bv[16];
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Bv[r] = 0.f;
+            if (has_bias) bias_load16(Bv, bpl, bfix, bstr, i0, half, a.Tq);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (BIAS && has_bias) b_wait<PC + 16>();
+        else
         b_wait<PC>();           // Q(t); dO(t) may still be on its way (first tile: the prologue has drained the queue)
         f32x16 S;
 #pragma unroll
@@ -519,7 +578,9 @@ __device__ __forceinline__ void battn_bwd_dkv_body(const BAttnArgs& a, const int
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int r = 4 * g + u;
-                const float p = __expf(bscore(S[r], a.scale, mk) - lsv[u]);
+                float sc = bscore(S[r], a.scale, mk);
+                if constexpr (BIAS) sc = __fadd_rn(sc, Bv[r]);
+                const float p = __expf(sc - lsv[u]);
                 float pk = p, dp = dP[r];
                 if (DROP) {
                     const bool keep = (kw & (1u << ((r & 3) + 8 * (r >> 2)))) != 0;
@@ -580,6 +641,24 @@ __global__ __launch_bounds__(64, 2) void battn_bwd_dv_kernel(const BAttnLaunch b
 template <int DP, bool DROP>
 __global__ __launch_bounds__(64, 2) void battn_bwd_dk_kernel(const BAttnLaunch b) { YT_BATTN_DECODE((battn_bwd_dkv_body<DP, DROP, 2>(a, bx, h, n))); }
 #undef YT_BATTN_DECODE
+#define YT_BATTN_DECODE_B(BODY_CALL)                                                                            \
+    const BAttnLaunch& b = bb.l;                                                                                \
+    const int raw = blockIdx.x;                                                                                 \
+    const int which = raw < b.nb0 ? 0 : 1;                                                                      \
+    const int bid = which ? xcd_remap(raw - b.nb0, (int)gridDim.x - b.nb0) : xcd_remap(raw, b.nb0);             \
+    const int gx = which ? b.gx1 : b.gx0;                                                                       \
+    const BAttnArgs& a = b.p[which];                                                                            \
+    const ytvln_attn_bias* bs = &bb.bias[which];                                                                \
+    const int bx = bid % gx, h = (bid / gx) % a.heads, n = bid / (gx * a.heads);                                \
+    BODY_CALL
+template <int DP, bool DROP>
+__global__ __launch_bounds__(64, 2) void battn_fwd_bias_kernel(const BAttnLaunchB bb) { YT_BATTN_DECODE_B((battn_fwd_body<DP, DROP, true>(a, bx, h, n, bs))); }
+template <int DP, bool DROP>
+__global__ __launch_bounds__(64, 2) void battn_bwd_dq_bias_kernel(const BAttnLaunchB bb) { YT_BATTN_DECODE_B((battn_bwd_dq_body<DP, DROP, true>(a, bx, h, n, bs))); }
+template <int DP, bool DROP>
+__global__ __launch_bounds__(64, DP == 128 ? BATTN_DKV_WPS : 2) void battn_bwd_dkv_bias_kernel(const BAttnLaunchB bb) { YT_BATTN_DECODE_B((battn_bwd_dkv_body<DP, DROP, 0, true>(a, bx, h, n, bs))); }
+// (no biased two-pass dV / dK forms: the dK pass sits at its 256 registers and would spill; biased launches take the one-pass kernel whatever ATTN_DKV_SPLIT says)
+#undef YT_BATTN_DECODE_B
 
 static int bcheck(const char* who, const BAttnArgs& a) {
     YT_REQUIRE(a.q && a.k && a.v, "%s: null q/k/v", who);
@@ -595,19 +674,22 @@ static int bcheck(const char* who, const BAttnArgs& a) {
     return 0;
 }
 
-#define YT_BLAUNCH(KERNEL, LDS)                                                                                        \
+#define YT_BLAUNCH(KERNEL, LDS, ARG)                                                                                   \
     do {                                                                                                              \
         if (a0.d == 128) {                                                                                            \
-            if (drop) hipLaunchKernelGGL((KERNEL<128, true>), dim3((unsigned)total), dim3(64), LDS, s, b);            \
-            else hipLaunchKernelGGL((KERNEL<128, false>), dim3((unsigned)total), dim3(64), LDS, s, b);                \
+            if (drop) hipLaunchKernelGGL((KERNEL<128, true>), dim3((unsigned)total), dim3(64), LDS, s, ARG);          \
+            else hipLaunchKernelGGL((KERNEL<128, false>), dim3((unsigned)total), dim3(64), LDS, s, ARG);              \
         } else {                                                                                                      \
-            if (drop) hipLaunchKernelGGL((KERNEL<64, true>), dim3((unsigned)total), dim3(64), LDS, s, b);             \
-            else hipLaunchKernelGGL((KERNEL<64, false>), dim3((unsigned)total), dim3(64), LDS, s, b);                 \
+            if (drop) hipLaunchKernelGGL((KERNEL<64, true>), dim3((unsigned)total), dim3(64), LDS, s, ARG);           \
+            else hipLaunchKernelGGL((KERNEL<64, false>), dim3((unsigned)total), dim3(64), LDS, s, ARG);               \
         }                                                                                                             \
     } while (0)
+static void bswap_problems(BAttnLaunchB& bb) { std::swap(bb.l.p[0], bb.l.p[1]); std::swap(bb.bias[0], bb.bias[1]); }
 
-static int blaunch_fwd(BAttnLaunch& b, int np, hipStream_t s) {
-    if (np > 1 && b.p[1].Tk > b.p[0].Tk) std::swap(b.p[0], b.p[1]);          // long workgroups first (attention.hip launch_bwd): forward walks key tiles
+static int blaunch_fwd(BAttnLaunchB& bb, int np, hipStream_t s) {
+    BAttnLaunch& b = bb.l;
+    const bool biased = bb.bias[0].ptr || (np > 1 && bb.bias[1].ptr);
+    if (np > 1 && b.p[1].Tk > b.p[0].Tk) bswap_problems(bb);          // long workgroups first (attention.hip launch_bwd): forward walks key tiles
     const BAttnArgs& a0 = b.p[0];
     bool drop = false;
     int maxTk = 0;
@@ -626,12 +708,15 @@ static int blaunch_fwd(BAttnLaunch& b, int np, hipStream_t s) {
     for (int i = 0; i < np; ++i)
         YT_REQUIRE(!drop || (b.p[i].keep && ((uintptr_t)b.p[i].keep & 127) == 0),
                    "attn_fwd_bf16: a launch with dropout needs a keep buffer (ytvln_attn_keep_bytes, 128-byte aligned) in every problem");
-    YT_BLAUNCH(battn_fwd_kernel, lds);
+    if (biased) YT_BLAUNCH(battn_fwd_bias_kernel, lds, bb);
+    else YT_BLAUNCH(battn_fwd_kernel, lds, b);
     YT_LAUNCH_CHECK("attn_fwd_bf16");
     return 0;
 }
 
-static int blaunch_bwd(BAttnLaunch& b, int np, hipStream_t s) {
+static int blaunch_bwd(BAttnLaunchB& bb, int np, hipStream_t s) {
+    BAttnLaunch& b = bb.l;
+    const bool biased = bb.bias[0].ptr || (np > 1 && bb.bias[1].ptr);
     const BAttnArgs& a0 = b.p[0];
     bool drop = false;
     int maxTq = 0, maxTk = 0;
@@ -650,31 +735,33 @@ static int blaunch_bwd(BAttnLaunch& b, int np, hipStream_t s) {
         YT_REQUIRE(!drop || (b.p[i].keep && ((uintptr_t)b.p[i].keep & 127) == 0),
                    "attn_bwd_bf16: a launch with dropout needs the keep buffers its forward wrote in every problem");
     {
-        if (np > 1 && b.p[1].Tk > b.p[0].Tk) std::swap(b.p[0], b.p[1]);      // dQ walks key tiles: the long-key direction first
+        if (np > 1 && b.p[1].Tk > b.p[0].Tk) bswap_problems(bb);      // dQ walks key tiles: the long-key direction first
         b.gx0 = (int)cdiv(b.p[0].Tq, 32);
         b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tq, 32) : 1;
         b.nb0 = b.gx0 * a0.heads * a0.N;
         const int64_t total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
         YT_REQUIRE(total < (1ll << 31), "attn_bwd_bf16: grid too large");
         const size_t lds = (size_t)2 * 32 * a0.d * 2 + (size_t)cdiv(maxTk, 32) * 32 * sizeof(float);
-        YT_BLAUNCH(battn_bwd_dq_kernel, lds);
+        if (biased) YT_BLAUNCH(battn_bwd_dq_bias_kernel, lds, bb);
+        else YT_BLAUNCH(battn_bwd_dq_kernel, lds, b);
     }
     {
-        if (np > 1 && b.p[1].Tq > b.p[0].Tq) std::swap(b.p[0], b.p[1]);      // dK/dV walks query tiles: the long-query direction first
+        if (np > 1 && b.p[1].Tq > b.p[0].Tq) bswap_problems(bb);      // dK/dV walks query tiles: the long-query direction first
         b.gx0 = (int)cdiv(b.p[0].Tk, 32);
         b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tk, 32) : 1;
         b.nb0 = b.gx0 * a0.heads * a0.N;
         const int64_t total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
         YT_REQUIRE(total < (1ll << 31), "attn_bwd_bf16: grid too large");
         const size_t lds = (size_t)2 * 32 * a0.d * 2 + (size_t)2 * cdiv(maxTq, 32) * 32 * sizeof(float);
-        if (a0.d == 128 && opt(OPT_ATTN_DKV_SPLIT)) {
+        if (a0.d == 128 && opt(OPT_ATTN_DKV_SPLIT) && !biased) {
             const size_t lds_v = (size_t)2 * 32 * a0.d * 2 + (size_t)cdiv(maxTq, 32) * 32 * sizeof(float);          // (no delta row in the dV pass)
             if (drop) { hipLaunchKernelGGL((battn_bwd_dv_kernel<128, true>), dim3((unsigned)total), dim3(64), lds_v, s, b);
                         hipLaunchKernelGGL((battn_bwd_dk_kernel<128, true>), dim3((unsigned)total), dim3(64), lds, s, b); }
             else { hipLaunchKernelGGL((battn_bwd_dv_kernel<128, false>), dim3((unsigned)total), dim3(64), lds_v, s, b);
                    hipLaunchKernelGGL((battn_bwd_dk_kernel<128, false>), dim3((unsigned)total), dim3(64), lds, s, b); }
         } else {
-            YT_BLAUNCH(battn_bwd_dkv_kernel, lds);
+            if (biased) YT_BLAUNCH(battn_bwd_dkv_bias_kernel, lds, bb);
+            else YT_BLAUNCH(battn_bwd_dkv_kernel, lds, b);
         }
     }
     YT_LAUNCH_CHECK("attn_bwd_bf16");
@@ -704,17 +791,47 @@ extern "C" int64_t ytvln_attn_keep_bytes(int N, int heads, int Tq, int Tk) {
 extern "C" int ytvln_attn_fwd_bf16(const ytvln_attn_problem* pa, const ytvln_attn_problem* pb, int N, int heads, int d, float scale,
                                    const int64_t* rng, void* stream) {
     YT_REQUIRE(pa, "attn_fwd_bf16: null problem");
-    BAttnLaunch b = {};
-    bfill(b.p[0], *pa, N, heads, d, scale, rng);
-    if (pb) bfill(b.p[1], *pb, N, heads, d, scale, rng);
+    BAttnLaunchB b = {};
+    bfill(b.l.p[0], *pa, N, heads, d, scale, rng);
+    if (pb) bfill(b.l.p[1], *pb, N, heads, d, scale, rng);
     return blaunch_fwd(b, pb ? 2 : 1, as_stream(stream));
 }
 
 extern "C" int ytvln_attn_bwd_bf16(const ytvln_attn_problem* pa, const ytvln_attn_problem* pb, int N, int heads, int d, float scale,
                                    const int64_t* rng, void* stream) {
     YT_REQUIRE(pa, "attn_bwd_bf16: null problem");
-    BAttnLaunch b = {};
-    bfill(b.p[0], *pa, N, heads, d, scale, rng);
-    if (pb) bfill(b.p[1], *pb, N, heads, d, scale, rng);
+    BAttnLaunchB b = {};
+    bfill(b.l.p[0], *pa, N, heads, d, scale, rng);
+    if (pb) bfill(b.l.p[1], *pb, N, heads, d, scale, rng);
     return blaunch_bwd(b, pb ? 2 : 1, as_stream(stream));
+}
+
+// ---- the same launches with a per-score additive bias (fp32) next to each problem (include/ytvln.h: ytvln_attn_bias) ---------------------------
+static int bbias_launch(bool backward, const char* who, const ytvln_attn_problem* pa, const ytvln_attn_bias* ba, const ytvln_attn_problem* pb,
+                        const ytvln_attn_bias* bbias, int N, int heads, int d, float scale, const int64_t* rng, void* stream) {
+    YT_REQUIRE(pa, "%s: null problem", who);
+    YT_REQUIRE(N > 0 && heads > 0 && d > 0, "%s: N, heads and d must be positive", who);
+    YT_REQUIRE(pa->Tq > 0 && pa->Tk > 0 && (!pb || (pb->Tq > 0 && pb->Tk > 0)), "%s: sequence lengths must be positive", who);
+    BAttnLaunchB b = {};
+    bfill(b.l.p[0], *pa, N, heads, d, scale, rng);
+    if (pb) bfill(b.l.p[1], *pb, N, heads, d, scale, rng);
+    const ytvln_attn_bias* src[2] = {ba, pb ? bbias : nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (src[i] && src[i]->ptr) {
+            const ytvln_attn_problem* pr = i ? pb : pa;
+            if (int rc = check_bias(who, *src[i], pr->Tq, pr->Tk)) return rc;
+            b.bias[i] = *src[i];
+        }
+    }
+    return backward ? blaunch_bwd(b, pb ? 2 : 1, as_stream(stream)) : blaunch_fwd(b, pb ? 2 : 1, as_stream(stream));
+}
+
+extern "C" int ytvln_attn_fwd_bias_bf16(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                                        const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream) {
+    return bbias_launch(false, "attn_fwd_bias_bf16", a, bias_a, b, bias_b, N, heads, d, scale, rng, stream);
+}
+
+extern "C" int ytvln_attn_bwd_bias_bf16(const ytvln_attn_problem* a, const ytvln_attn_bias* bias_a, const ytvln_attn_problem* b,
+                                        const ytvln_attn_bias* bias_b, int N, int heads, int d, float scale, const int64_t* rng, void* stream) {
+    return bbias_launch(true, "attn_bwd_bias_bf16", a, bias_a, b, bias_b, N, heads, d, scale, rng, stream);
 }

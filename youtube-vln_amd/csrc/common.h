@@ -125,6 +125,27 @@ __device__ __forceinline__ uint32_t attn_drop_hash(uint32_t lo, uint32_t hi, con
     return (uint32_t)__umul24(x, 0xB5297Au);
 }
 
+// ---- per-score additive attention bias (ytvln_attn_bias of include/ytvln.h) -------------------------------------------------------------
+// bias[n, h, i, j] = ptr[n * stride_n + h * stride_h + i * stride_q + j * stride_k] is added to score (i, j) after the key mask
+// (vilbert.py:581-582, 603-604).  Every attention kernel holds a 32x32 block of scores as 16 registers per lane: one coordinate is the lane's
+// own (query in the forward / dQ kernels, key in the dK/dV kernels), the other runs down the registers in krow order.
+int check_bias(const char* who, const ytvln_attn_bias& b, int Tq, int Tk);          // host: alignment, stride signs, 32-bit plane (attention.hip)
+__device__ __forceinline__ const float* bias_plane(const ytvln_attn_bias& b, int n, int h) {
+    return b.ptr + (int64_t)n * b.stride_n + (int64_t)h * b.stride_h;
+}
+// B[r] = plane[fixed + (i0 + krow(r, half)) * stride]: `plane` is wave-uniform (scalar base), `fixed` the offset of the lane's own coordinate;
+// offsets inside a (pair, head) plane are 32-bit (the entry points check (Tq-1) stride_q + (Tk-1) stride_k < 2^31), so an address costs one
+// register.  Rows past the end repeat the last row: such a score is masked out anyway (a key past the end carries a -inf mask, a query past
+// the end a +inf lse) and a legal bias value, finite or -inf, keeps it so.  Loads only -- no use of the values here, so the wait for them sits
+// where the caller adds them.  Plain dword loads: any stride, 4-byte alignment.
+__device__ __forceinline__ float bias_at(const float* __restrict__ plane, uint32_t fixed, int stride, int i, int nrows) {
+    return plane[fixed + (uint32_t)(min(i, nrows - 1) * stride)];
+}
+__device__ __forceinline__ void bias_load16(float (&B)[16], const float* __restrict__ plane, uint32_t fixed, int stride, int i0, int half, int nrows) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) B[r] = bias_at(plane, fixed, stride, i0 + (r & 3) + 8 * (r >> 2) + 4 * half, nrows);
+}
+
 // ---- wave / block reductions ------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

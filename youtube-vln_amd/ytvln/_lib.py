@@ -30,6 +30,11 @@ class AttnProblem(C.Structure):
                [("Tq", C.c_int32), ("Tk", C.c_int32), ("p_drop", C.c_float), ("reserved", C.c_int32), ("site", C.c_int64), ("keep", C.c_void_p)]
 
 
+class AttnBias(C.Structure):
+    """`ytvln_attn_bias` of include/ytvln.h: fp32 bias[n,h,i,j] = ptr[n*stride_n + h*stride_h + i*stride_q + j*stride_k] (strides in elements)."""
+    _fields_ = [("ptr", C.c_void_p)] + [(n, C.c_int64) for n in ("stride_n", "stride_h", "stride_q", "stride_k")]
+
+
 SIGNATURES = {
     "ytvln_gemm_workspace_elems": [I32, I32, I32, I32],
     "ytvln_gemm_f32": [P, I64, I32, P, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, I32, P],
@@ -49,6 +54,12 @@ SIGNATURES = {
     "ytvln_attn_keep_bytes": [I32, I32, I32, I32],
     "ytvln_attn_fwd_bf16": [P, P, I32, I32, I32, F32, P, P],
     "ytvln_attn_bwd_bf16": [P, P, I32, I32, I32, F32, P, P],
+    "ytvln_attn_bias_size": [],
+    "ytvln_attn_fwd_bias_f32": [P, P, P, P, I32, I32, I32, F32, P, P],
+    "ytvln_attn_bwd_bias_f32": [P, P, P, P, I32, I32, I32, F32, P, P],
+    "ytvln_attn_fwd_bias_bf16": [P, P, P, P, I32, I32, I32, F32, P, P],
+    "ytvln_attn_bwd_bias_bf16": [P, P, P, P, I32, I32, I32, F32, P, P],
+    "ytvln_attn_probs_bias_f32": [P, I64, P, I64, P, P, P, P, I32, I32, I32, I32, I32, F32, P],
     "ytvln_attn_fwd_pair": [P, P, I32, I32, I32, F32, P, P],
     "ytvln_attn_bwd_pair": [P, P, I32, I32, I32, F32, P, P],
     "ytvln_gemm_plan": [I32, I32, I32, I32, I32, P, P, P],
@@ -107,7 +118,7 @@ SIGNATURES = {
     "ytvln_rccl_async_error": [P],
     "ytvln_rccl_destroy": [P],
 }
-RESTYPES = {"ytvln_attn_problem_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
+RESTYPES = {"ytvln_attn_problem_size": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
 DT_F32, DT_F64, DT_BF16, DT_I64, DT_U8 = 0, 1, 2, 3, 4
 RED_SUM, RED_MAX, RED_MIN = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
@@ -149,6 +160,8 @@ def load():
         raise YtvlnLibraryError(f"ABI mismatch: library {lib.ytvln_version()} != binding {ABI_VERSION}")
     if lib.ytvln_attn_problem_size() != C.sizeof(AttnProblem):          # a record the library would read past
         raise YtvlnLibraryError(f"ytvln_attn_problem: library {lib.ytvln_attn_problem_size()} bytes != binding {C.sizeof(AttnProblem)}")
+    if lib.ytvln_attn_bias_size() != C.sizeof(AttnBias):
+        raise YtvlnLibraryError(f"ytvln_attn_bias: library {lib.ytvln_attn_bias_size()} bytes != binding {C.sizeof(AttnBias)}")
     _lib = lib
     _FN.update({name: getattr(lib, name) for name in SIGNATURES})
     return lib

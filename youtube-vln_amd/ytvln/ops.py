@@ -1386,6 +1386,36 @@ def _attn_problem(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, Tq, Tk, p, 
     return pr
 
 
+def attn_bias_strides(bias: Tensor, N: int, heads: int, Tq: int, Tk: int) -> Tuple[int, int, int, int]:
+    """(stride_n, stride_h, stride_q, stride_k) in elements of a bias that broadcasts against the scores [N, heads, Tq, Tk]
+    (`ytvln_attn_bias`, include/ytvln.h): a 4-D tensor or view of shape [N or 1, heads or 1, Tq, Tk], read as it lies -- a dimension of
+    size 1 (or an expanded one) gets stride 0, and the transposed view of an [.., Tk, Tq] tensor simply arrives with its strides swapped."""
+    if bias.dim() != 4 or bias.shape[0] not in (1, N) or bias.shape[1] not in (1, heads) or tuple(bias.shape[2:]) != (Tq, Tk):
+        raise NotImplementedError(f"attention bias of shape {tuple(bias.shape)}: accepted are [N,1,Tq,Tk], [N,heads,Tq,Tk] and [1,1,Tq,Tk] "
+                                  f"(N {N}, heads {heads}, Tq {Tq}, Tk {Tk}) or views of those shapes")
+    sn, sh, sq, sk = (0 if bias.shape[i] == 1 else int(bias.stride(i)) for i in range(4))
+    if sq < 0 or sk < 0:
+        raise NotImplementedError("attention bias: negative strides over queries / keys are not supported")
+    return sn, sh, sq, sk
+
+
+def _attn_bias(bias: Optional[Tensor], N: int, heads: int, Tq: int, Tk: int):
+    """-> (the tensor the record points into -- keep it alive --, `ytvln_attn_bias` record), or (None, None).  Only an unsupported dtype is
+    converted; a non-contiguous view is passed as it lies.  The bias is a constant of the attention: one that requires grad is refused."""
+    if bias is None:
+        return None, None
+    if bias.requires_grad:
+        raise RuntimeError("attention bias with requires_grad=True: no gradient with respect to the bias is computed (detach it)")
+    if not bias.is_cuda:
+        raise RuntimeError("attention bias must live on the GPU (no CPU fallback)")
+    if bias.dtype != torch.float32:
+        bias = bias.float()
+    rec = _lib.AttnBias()
+    rec.ptr = bias.data_ptr()
+    rec.stride_n, rec.stride_h, rec.stride_q, rec.stride_k = attn_bias_strides(bias, N, heads, Tq, Tk)
+    return bias, rec
+
+
 def _attn_keep(N, heads, Tq, Tk, p, device):
     """bf16-resident attention with dropout: the buffer the forward kernel writes its keep decisions to and the backward kernels read them from
     (`ytvln_attn_problem.keep`); None without dropout."""
@@ -1394,10 +1424,15 @@ def _attn_keep(N, heads, Tq, Tk, p, device):
     return torch.empty(int(_lib.load().ytvln_attn_keep_bytes(N, heads, Tq, Tk)), dtype=torch.uint8, device=device)
 
 
-def _attn_launch(backward: bool, bf16: bool, pa, pb, N, heads, d, scale, rng):
-    """One launch over one problem (pb = None) or the two directions of BertBiAttention."""
+def _attn_launch(backward: bool, bf16: bool, pa, pb, N, heads, d, scale, rng, ba=None, bb=None):
+    """One launch over one problem (pb = None) or the two directions of BertBiAttention; ba / bb: `ytvln_attn_bias` records of the problems
+    (launches without one take the entry points they always took)."""
     rp = _ptr(rng) if rng is not None else None
-    if bf16:
+    if ba is not None or bb is not None:
+        name = "ytvln_attn_%s_bias_%s" % ("bwd" if backward else "fwd", "bf16" if bf16 else "f32")
+        call(name, ctypes.addressof(pa), ctypes.addressof(ba) if ba is not None else None, ctypes.addressof(pb) if pb is not None else None,
+             ctypes.addressof(bb) if bb is not None else None, N, heads, d, float(scale), rp, _stream())
+    elif bf16:
         call("ytvln_attn_bwd_bf16" if backward else "ytvln_attn_fwd_bf16", ctypes.addressof(pa), ctypes.addressof(pb) if pb is not None else None,
              N, heads, d, float(scale), rp, _stream())
     else:
@@ -1405,12 +1440,14 @@ def _attn_launch(backward: bool, bf16: bool, pa, pb, N, heads, d, scale, rng):
              rp, _stream())
 
 
-def _attn_fwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, N, heads, Tq, Tk, d, scale, p, rng, site):
+def _attn_fwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, N, heads, Tq, Tk, d, scale, p, rng, site, bias=None):
     lse = torch.empty((N, heads, Tq), dtype=torch.float32, device=out.device)
-    if q.dtype == torch.bfloat16:
-        keep = _attn_keep(N, heads, Tq, Tk, p, out.device)
-        _attn_launch(False, True, _attn_problem(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, Tq, Tk, p, site, ctx=out, lse=lse, keep=keep),
-                     None, N, heads, d, scale, rng)
+    bias, brec = _attn_bias(bias, N, heads, Tq, Tk)
+    if q.dtype == torch.bfloat16 or brec is not None:
+        bf16 = q.dtype == torch.bfloat16
+        keep = _attn_keep(N, heads, Tq, Tk, p, out.device) if bf16 else None
+        _attn_launch(False, bf16, _attn_problem(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, Tq, Tk, p, site, ctx=out, lse=lse, keep=keep),
+                     None, N, heads, d, scale, rng, ba=brec)
         lse._ytvln_keep = keep          # direct callers hand `lse` to _attn_bwd, which finds the forward's keep decisions here; the autograd
         return lse                      # functions save the buffer explicitly (a saved tensor is unpacked into a new Python object)
     call("ytvln_attn_fwd_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(v, v_off), ldv, _ptr(mask), _ptr(out), out.shape[-1],
@@ -1419,23 +1456,25 @@ def _attn_fwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, N, heads, 
 
 
 def _attn_bwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, dout, lse, dq, dq_off, lddq, dk, dk_off, lddk, dv, dv_off,
-              lddv, N, heads, Tq, Tk, d, scale, p, rng, site, keep=None):
+              lddv, N, heads, Tq, Tk, d, scale, p, rng, site, keep=None, bias=None):
     delta = torch.empty_like(lse)
-    if q.dtype == torch.bfloat16:
+    bias, brec = _attn_bias(bias, N, heads, Tq, Tk)
+    if q.dtype == torch.bfloat16 or brec is not None:
+        bf16 = q.dtype == torch.bfloat16
         if keep is None:
             keep = getattr(lse, "_ytvln_keep", None)
-        if p > 0 and keep is None:
+        if bf16 and p > 0 and keep is None:
             raise RuntimeError("bf16 attention backward with dropout needs the keep decisions its forward wrote (pass keep= or the lse tensor _attn_fwd returned)")
-        _attn_launch(True, True, _attn_problem(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, Tq, Tk, p, site, ctx_in=out, dctx=dout,
+        _attn_launch(True, bf16, _attn_problem(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, Tq, Tk, p, site, ctx_in=out, dctx=dout,
                                                lse_in=lse, delta=delta, dq=dq, dq_off=dq_off, lddq=lddq, dk=dk, dk_off=dk_off, lddk=lddk,
-                                               dv=dv, dv_off=dv_off, lddv=lddv, keep=keep), None, N, heads, d, scale, rng)
+                                               dv=dv, dv_off=dv_off, lddv=lddv, keep=keep), None, N, heads, d, scale, rng, ba=brec)
         return
     call("ytvln_attn_bwd_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(v, v_off), ldv, _ptr(mask), _ptr(out), _ptr(dout),
          out.shape[-1], _ptr(lse), _ptr(delta), _ptr(dq, dq_off), lddq, _ptr(dk, dk_off), lddk, _ptr(dv, dv_off), lddv, N, heads, Tq,
          Tk, d, float(scale), float(p), _ptr(rng) if rng is not None else None, int(site), _stream())
 
 
-def attn_probs(q, q_off, ldq, k, k_off, ldk, mask, lse, N, heads, Tq, Tk, d, scale) -> Tensor:
+def attn_probs(q, q_off, ldq, k, k_off, ldk, mask, lse, N, heads, Tq, Tk, d, scale, bias=None) -> Tensor:
     probs = torch.empty((N, heads, Tq, Tk), dtype=torch.float32, device=lse.device)
     if q.dtype == torch.bfloat16 or k.dtype == torch.bfloat16:
         # bf16-resident path (output_all_attention_masks is a rare diagnostic there): the probability kernel reads fp32 rows, so the
@@ -1443,16 +1482,24 @@ def attn_probs(q, q_off, ldq, k, k_off, ldk, mask, lse, N, heads, Tq, Tk, d, sca
         q, k = q.float(), k.float()
     elif q.dtype != torch.float32 or k.dtype != torch.float32:
         raise RuntimeError(f"attn_probs: q / k must be float32 or bfloat16, got {q.dtype} / {k.dtype}")
+    bias, brec = _attn_bias(bias, N, heads, Tq, Tk)
+    if brec is not None:
+        call("ytvln_attn_probs_bias_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(mask), ctypes.addressof(brec), _ptr(lse), _ptr(probs),
+             N, heads, Tq, Tk, d, float(scale), _stream())
+        return probs
     call("ytvln_attn_probs_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(mask), _ptr(lse), _ptr(probs), N, heads, Tq, Tk, d,
          float(scale), _stream())
     return probs
 
 
 class SelfAttentionFn(torch.autograd.Function):
-    """ctx = MHA(qkv) for a packed [N*T, 3H] projection (query | key | value column blocks); vilbert.py:284-311."""
+    """ctx = MHA(qkv) for a packed [N*T, 3H] projection (query | key | value column blocks); vilbert.py:284-311.
+    Optional ninth argument: a per-score additive bias (see `attn_bias_strides`); `mask` may then be None."""
 
     @staticmethod
-    def forward(ctx, qkv, mask, N, T, heads, p, rng, site):
+    def forward(ctx, qkv, mask, N, T, heads, p, rng, site, *opt):
+        bias = opt[0] if opt else None
+        ctx.n_in = 8 + len(opt)
         ctx.set_materialize_grads(False)
         _check(qkv, "qkv", qkv.dtype if qkv.dtype == torch.bfloat16 else torch.float32)
         assert qkv.is_contiguous() and qkv.dim() == 2 and qkv.shape[0] == N * T
@@ -1462,26 +1509,26 @@ class SelfAttentionFn(torch.autograd.Function):
             raise NotImplementedError(f"bf16-resident attention is built for head dimensions 64 and 128 (got {d}); use the fp32 path")
         scale = 1.0 / math.sqrt(d)
         out = torch.empty((N * T, H), dtype=qkv.dtype, device=qkv.device)
-        lse = _attn_fwd(qkv, 0, 3 * H, qkv, H, 3 * H, qkv, 2 * H, 3 * H, mask, out, N, heads, T, T, d, scale, p, rng, site)
+        lse = _attn_fwd(qkv, 0, 3 * H, qkv, H, 3 * H, qkv, 2 * H, 3 * H, mask, out, N, heads, T, T, d, scale, p, rng, site, bias=bias)
         keep = getattr(lse, "_ytvln_keep", None)
         ctx.meta = (N, T, heads, H, d, scale, p, site)
-        ctx.save_for_backward(qkv, mask, out, lse, rng, keep)
+        ctx.save_for_backward(qkv, mask, out, lse, rng, keep, bias)          # (the bias by reference: no copy)
         ctx.mark_non_differentiable(lse)
         return out, lse
 
     @staticmethod
     def backward(ctx, dout, _dlse):
         if dout is None:
-            return (None,) * 8
-        qkv, mask, out, lse, rng, keep = ctx.saved_tensors
+            return (None,) * ctx.n_in
+        qkv, mask, out, lse, rng, keep, bias = ctx.saved_tensors
         N, T, heads, H, d, scale, p, site = ctx.meta
         dout = dout if dout.is_contiguous() else dout.contiguous()
         if dout.dtype != qkv.dtype:
             dout = dout.to(qkv.dtype)
         dqkv = torch.empty_like(qkv)
         _attn_bwd(qkv, 0, 3 * H, qkv, H, 3 * H, qkv, 2 * H, 3 * H, mask, out, dout, lse, dqkv, 0, 3 * H, dqkv, H, 3 * H, dqkv, 2 * H,
-                  3 * H, N, heads, T, T, d, scale, p, rng, site, keep=keep)
-        return dqkv, None, None, None, None, None, None, None
+                  3 * H, N, heads, T, T, d, scale, p, rng, site, keep=keep, bias=bias)
+        return (dqkv,) + (None,) * (ctx.n_in - 1)
 
 
 class CoAttentionFn(torch.autograd.Function):
@@ -1493,7 +1540,12 @@ class CoAttentionFn(torch.autograd.Function):
         ctx1 [N*T, Hb] = attend(q2; kv1, image mask)     ctx2 [N*R, Hb] = attend(q1; kv2, text mask)"""
 
     @staticmethod
-    def forward(ctx, q1, kv1, q2, kv2, mask1, mask2, N, R, T, heads, p1, p2, rng, site1, site2):
+    def forward(ctx, q1, kv1, q2, kv2, mask1, mask2, N, R, T, heads, p1, p2, rng, site1, site2, *opt):
+        """opt: (bias1, bias2) -- per-score biases of the two directions, [.., T, R] for ctx1 and [.., R, T] for ctx2 (either may be None)."""
+        bias1, bias2 = (tuple(opt) + (None, None))[:2]
+        ctx.n_in = 15 + len(opt)
+        bias1, b1 = _attn_bias(bias1, N, heads, T, R)
+        bias2, b2 = _attn_bias(bias2, N, heads, R, T)
         bf16 = q1.dtype == torch.bfloat16
         for t, nme in ((q1, "q1"), (kv1, "kv1"), (q2, "q2"), (kv2, "kv2")):
             _check(t, nme, torch.bfloat16 if bf16 else torch.float32)
@@ -1514,17 +1566,18 @@ class CoAttentionFn(torch.autograd.Function):
         _attn_launch(False, bf16,
                      _attn_problem(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, T, R, p1, site1, ctx=ctx1, lse=lse1, keep=keep1),
                      _attn_problem(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, R, T, p2, site2, ctx=ctx2, lse=lse2, keep=keep2),
-                     N, heads, d, scale, rng)
+                     N, heads, d, scale, rng, ba=b1, bb=b2)
         ctx.meta = (N, R, T, heads, Hb, d, scale, p1, p2, site1, site2)
-        ctx.save_for_backward(q1, kv1, q2, kv2, mask1, mask2, ctx1, ctx2, lse1, lse2, rng, keep1, keep2)
+        ctx.save_for_backward(q1, kv1, q2, kv2, mask1, mask2, ctx1, ctx2, lse1, lse2, rng, keep1, keep2, bias1, bias2)
         ctx.mark_non_differentiable(lse1, lse2)
         ctx.set_materialize_grads(False)
         return ctx1, ctx2, lse1, lse2
 
     @staticmethod
     def backward(ctx, d1, d2, _a, _b):
-        q1, kv1, q2, kv2, mask1, mask2, ctx1, ctx2, lse1, lse2, rng, keep1, keep2 = ctx.saved_tensors
+        q1, kv1, q2, kv2, mask1, mask2, ctx1, ctx2, lse1, lse2, rng, keep1, keep2, bias1, bias2 = ctx.saved_tensors
         N, R, T, heads, Hb, d, scale, p1, p2, site1, site2 = ctx.meta
+        nn_ = (None,) * (ctx.n_in - 4)
         gq1 = gkv1 = gq2 = gkv2 = None
         if d1 is not None and d2 is not None:       # the usual case: both directions in one launch per kernel
             d1 = d1 if d1.is_contiguous() else d1.contiguous()
@@ -1536,19 +1589,19 @@ class CoAttentionFn(torch.autograd.Function):
                                      delta=delta1, dq=gq2, lddq=Hb, dk=gkv1, lddk=2 * Hb, dv=gkv1, dv_off=Hb, lddv=2 * Hb, keep=keep1),
                        _attn_problem(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, R, T, p2, site2, ctx_in=ctx2, dctx=d2, lse_in=lse2,
                                      delta=delta2, dq=gq1, lddq=Hb, dk=gkv2, lddk=2 * Hb, dv=gkv2, dv_off=Hb, lddv=2 * Hb, keep=keep2),
-                       N, heads, d, scale, rng)
-            return (gq1, gkv1, gq2, gkv2) + (None,) * 11
+                       N, heads, d, scale, rng, ba=_attn_bias(bias1, N, heads, T, R)[1], bb=_attn_bias(bias2, N, heads, R, T)[1])
+            return (gq1, gkv1, gq2, gkv2) + nn_
         if d1 is not None:      # text queries over image keys/values -> dq2, dk1|dv1
             d1 = d1 if d1.is_contiguous() else d1.contiguous()
             gq2, gkv1 = torch.empty_like(q2), torch.empty_like(kv1)
             _attn_bwd(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, ctx1, d1, lse1, gq2, 0, Hb, gkv1, 0, 2 * Hb, gkv1, Hb,
-                      2 * Hb, N, heads, T, R, d, scale, p1, rng, site1, keep=keep1)
+                      2 * Hb, N, heads, T, R, d, scale, p1, rng, site1, keep=keep1, bias=bias1)
         if d2 is not None:      # image queries over text keys/values -> dq1, dk2|dv2
             d2 = d2 if d2.is_contiguous() else d2.contiguous()
             gq1, gkv2 = torch.empty_like(q1), torch.empty_like(kv2)
             _attn_bwd(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, ctx2, d2, lse2, gq1, 0, Hb, gkv2, 0, 2 * Hb, gkv2, Hb,
-                      2 * Hb, N, heads, R, T, d, scale, p2, rng, site2, keep=keep2)
-        return (gq1, gkv1, gq2, gkv2) + (None,) * 11
+                      2 * Hb, N, heads, R, T, d, scale, p2, rng, site2, keep=keep2, bias=bias2)
+        return (gq1, gkv1, gq2, gkv2) + nn_
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -173,6 +173,19 @@ def _mask2d(mask: torch.Tensor, n: int, t: int) -> torch.Tensor:
     return m.contiguous()
 
 
+def _self_mask(mask: torch.Tensor, n: int, t: int, heads: int):
+    """(per-key mask [N, T] or None, per-score bias or None) of a self-attention `attention_mask`.  N*T elements: the per-key path, exactly as
+    before.  [N,1,T,T], [N,heads,T,T] and [1,1,T,T] -- anything else the reference's `attention_scores + attention_mask` broadcast
+    (vilbert.py:294-297, 423-427) would take is refused -- go to the kernels' bias operand, read in place, with no key mask."""
+    if mask.numel() == n * t and (mask.dim() != 4 or mask.shape[2] == 1):
+        return _mask2d(mask, n, t), None
+    if mask.dim() == 4 and tuple(mask.shape[2:]) == (t, t) and mask.shape[0] in (1, n) and mask.shape[1] in (1, heads) \
+            and (mask.shape[0] == n or mask.shape[1] == 1):
+        return None, mask
+    raise NotImplementedError(f"attention mask of shape {tuple(mask.shape)}: accepted are per-key masks of N*T elements ([N,1,1,T]) and "
+                              f"per-score masks [N,1,T,T], [N,heads,T,T], [1,1,T,T] (N {n}, heads {heads}, T {t})")
+
+
 class BertLayerNorm(nn.Module):
     """TF-style LayerNorm, eps inside the sqrt (vilbert.py:204-217) -- fused kernel."""
 
@@ -243,19 +256,22 @@ class _SelfAttentionBase(nn.Module):
         """(context, probs, hidden_states-for-the-residual): the third value is what the caller's `LayerNorm(dense(context) + input)`
         must use as `input` so that the two gradients of `hidden_states` meet inside the projection's input-gradient GEMM."""
         n, t, _ = hidden_states.shape
-        mask = _mask2d(attention_mask, n, t)
+        mask, bias = _self_mask(attention_mask, n, t, self.num_attention_heads)
         qkv, residual = _PackedQKV.project_res(hidden_states, self.query, self.key, self.value)
         qkv = qkv.view(n * t, 3 * self.all_head_size)
         p = _p(self, self.dropout.p)
         st = _drop_state(self, qkv) if p > 0 else None
+        extra = () if bias is None else (bias,)          # (no bias: the call, and the launch behind it, as it always was)
+        if bias is not None and bias.is_cuda and ops.TwoStream.active:
+            bias.record_stream(torch.cuda.current_stream())          # the text layers run on the side stream: a full mask made on the main one is read there
         out, lse = ops.SelfAttentionFn.apply(qkv, mask, n, t, self.num_attention_heads, p, st.tensor if st else None,
-                                             st.next_site() if st else 0)
+                                             st.next_site() if st else 0, *extra)
         probs = None
         if self.want_probs:
             with torch.no_grad():
                 h = self.all_head_size
                 probs = ops.attn_probs(qkv, 0, 3 * h, qkv, h, 3 * h, mask, lse, n, self.num_attention_heads, t, t,
-                                       self.attention_head_size, 1.0 / math.sqrt(self.attention_head_size))
+                                       self.attention_head_size, 1.0 / math.sqrt(self.attention_head_size), bias=bias)
         return out.view(n, t, self.all_head_size), probs, residual
 
 
@@ -424,11 +440,18 @@ class BertBiAttention(nn.Module):
         """forward() plus the two stream inputs as they leave the projections' autograd nodes (the residual values BertBiOutput adds):
         returned, not parked on the module -- no graph stays pinned between calls and a direct forward() cannot leave a stale pair behind
         (ADVICE r2).  BertConnectionLayer calls this form."""
-        if use_co_attention_mask:
-            raise NotImplementedError("use_co_attention_mask=True is dead code in the reference (vilbert.py:736) and unsupported here")
         n, r, _ = input_tensor1.shape
         t = input_tensor2.shape[1]
         hb = self.all_head_size
+        # use_co_attention_mask (vilbert.py:581-582, 603-604): co_attention_mask [N,1,R,T] is added to the scores of regions over tokens as it is
+        # and to those of tokens over regions through its transposed VIEW (the kernels read it through swapped strides: no copy)
+        bias1 = bias2 = None
+        if use_co_attention_mask:
+            if co_attention_mask is None or co_attention_mask.dim() != 4 or tuple(co_attention_mask.shape[2:]) != (r, t):
+                raise NotImplementedError("use_co_attention_mask=True needs a co_attention_mask of shape [N,1,R,T] (or [N,heads,R,T], [1,1,R,T]), got "
+                                          f"{None if co_attention_mask is None else tuple(co_attention_mask.shape)}")
+            bias2 = co_attention_mask if co_attention_mask.dtype == torch.float32 else co_attention_mask.float()
+            bias1 = bias2.transpose(2, 3)
         m1, m2 = _mask2d(attention_mask1, n, r), _mask2d(attention_mask2, n, t)
         # each stream's input feeds two projections and the residual of BertBiOutput: the residual value travels through both
         # projections' autograd nodes (ops.LinearFn passthrough) so the three gradients meet inside the input-gradient GEMMs
@@ -442,17 +465,18 @@ class BertBiAttention(nn.Module):
         p1, p2 = _p(self, self.dropout1.p), _p(self, self.dropout2.p)
         st = _drop_state(self, q1) if (p1 > 0 or p2 > 0) else None
         s1, s2 = (st.next_site(), st.next_site()) if st else (0, 0)
+        extra = () if bias2 is None else (bias1, bias2)
         ctx1, ctx2, lse1, lse2 = ops.CoAttentionFn.apply(q1, kv1, q2, kv2, m1, m2, n, r, t, self.num_attention_heads, p1, p2,
-                                                         st.tensor if st else None, s1, s2)
+                                                         st.tensor if st else None, s1, s2, *extra)
         ops.TwoStream.mark()                            # both context tensors exist: the text side may go on from here
         probs = (None, None)
         if self.want_probs:
             with torch.no_grad():
                 sc = 1.0 / math.sqrt(self.attention_head_size)
                 pr1 = ops.attn_probs(q2, 0, hb, kv1, 0, 2 * hb, m1, lse1, n, self.num_attention_heads, t, r,
-                                     self.attention_head_size, sc)
+                                     self.attention_head_size, sc, bias=bias1)
                 pr2 = ops.attn_probs(q1, 0, hb, kv2, 0, 2 * hb, m2, lse2, n, self.num_attention_heads, r, t,
-                                     self.attention_head_size, sc)
+                                     self.attention_head_size, sc, bias=bias2)
                 probs = (pr1, pr2)
         return ctx1.view(n, t, hb), ctx2.view(n, r, hb), probs, res1, res2
 
@@ -504,6 +528,11 @@ class BertConnectionLayer(nn.Module):
 
 
 class BertEncoder(nn.Module):
+    # Extension (not a BertConfig field: the config stays the reference's strict dataclass).  The reference hard-codes this switch to False as a
+    # local of its forward (vilbert.py:736), and False -- parity with it -- is the default here.  Set `encoder.use_co_attention_mask = True` to
+    # hand `co_attention_mask` to every connection layer (BertBiAttention adds it to the scores, vilbert.py:581-582, 603-604).
+    use_co_attention_mask = False
+
     def __init__(self, config):
         super().__init__()
         self.FAST_MODE = config.fast_mode
@@ -591,6 +620,8 @@ class BertEncoder(nn.Module):
                 image_attention_mask = image_attention_mask.reshape(b, -1).unsqueeze(0).expand(b, b, r_).contiguous().view(b * b, 1, 1, r_)
                 txt_embedding = txt_embedding.unsqueeze(1).expand(b, b, t_, ht).contiguous().view(b * b, t_, ht)
                 txt_attention_mask = txt_attention_mask.reshape(b, -1).unsqueeze(1).expand(b, b, t_).contiguous().view(b * b, 1, 1, t_)
+                if self.use_co_attention_mask and co_attention_mask is not None:          # row (i, j) takes text i's mask (vilbert.py:778)
+                    co_attention_mask = co_attention_mask.unsqueeze(1).expand(b, b, 1, r_, t_).contiguous().view(b * b, 1, r_, t_)
             if count == 0 and self.FAST_MODE:
                 # one text against many images (vilbert.py:780-782): the text rows are broadcast to the image batch
                 nb = image_embedding.size(0)
@@ -599,7 +630,8 @@ class BertEncoder(nn.Module):
                     nb, 1, 1, txt_embedding.size(1))
             if self.with_coattention:
                 image_embedding, txt_embedding, co_probs = self.c_layer[count](
-                    image_embedding, image_attention_mask, txt_embedding, txt_attention_mask, co_attention_mask, False)
+                    image_embedding, image_attention_mask, txt_embedding, txt_attention_mask, co_attention_mask,
+                    bool(self.use_co_attention_mask))
                 if output_all_attention_masks:
                     att_c.append(co_probs)
                 if cuts:
@@ -841,7 +873,14 @@ class BertModel(BertPreTrainedModel):
             ext_v = torch.zeros((nv, 1, 1, r), dtype=torch.float32, device=input_txt.device)
         else:
             ext_v = ((1.0 - image_attention_mask.to(torch.float32)) * -10000.0).view(nv, 1, 1, r)
-        # co_attention_mask only feeds the dead use_co_attention_mask branch (vilbert.py:736): not materialised.
+        # co_attention_mask only feeds the use_co_attention_mask branch, which the reference switches off (vilbert.py:736): materialised
+        # (vilbert.py:1289-1298: zeros when None, unsqueeze(1) * 5.0, fp32) only when the encoder's switch is on
+        ext_co = None
+        if self.encoder.use_co_attention_mask:
+            if co_attention_mask is None:
+                ext_co = torch.zeros((n, 1, r, t), dtype=torch.float32, device=input_txt.device)
+            else:
+                ext_co = (co_attention_mask.unsqueeze(1) * 5.0).to(torch.float32)
 
         ts = ops.TwoStream
         try:
@@ -852,7 +891,7 @@ class BertModel(BertPreTrainedModel):
                 embedding_output = self.embeddings(input_txt, token_type_ids)
             v_embedding_output = self.v_embeddings(input_imgs, image_loc)
             encoded_layers_t, encoded_layers_v, all_attention_mask = self.encoder(
-                embedding_output, v_embedding_output, ext_t, ext_v, None,
+                embedding_output, v_embedding_output, ext_t, ext_v, ext_co,
                 output_all_encoded_layers=output_all_encoded_layers, output_all_attention_masks=output_all_attention_masks)
         finally:
             ts.active = False
