@@ -400,6 +400,25 @@ int ytvln_adamw_f32_gbf16(float* p, const uint16_t* g_bf16, float* m, float* v, 
 /* g_bf16[o : o+len] = bf16(g[o : o+len]) (round to nearest even) for every record of an AdamW chunk table: the send buffer of the bf16
  * exchange, one workgroup per record; elements outside the table are not written.  Both bases 16-byte aligned. */
 int ytvln_grad_pack_bf16(const float* g, uint16_t* g_bf16, const void* chunks, int nchunks, void* stream);
+/* Global gradient-norm clipping fused into the step (the reference has none; torch.nn.utils.clip_grad_norm_ semantics), three launches:
+ * ytvln_grad_sumsq -> ytvln_grad_clip_coef -> ytvln_adamw_clip.  No atomics, every summation order fixed: results are reproducible bit
+ * for bit.  `dtype` / `g_dtype`: YTVLN_DT_F32 (the fp32 gradient arena) or YTVLN_DT_BF16 (the bf16 sums of the bf16 exchange), nothing else.
+ *   partials[i] = sum of g[o : o+len]^2 over record i of an AdamW chunk table, accumulated in fp32: one workgroup and one float per record.
+ * g 16-byte aligned; reads 4 (bf16: 2) bytes per element. */
+int ytvln_grad_sumsq(const void* g, int dtype, const void* chunks, int nchunks, float* partials, void* stream);
+/* Sigma = sum of the n partials (of every table of the step) in fp64, then the DEVICE record clip[0..3] (16-byte aligned):
+ *   clip[0] = norm = grad_scale * sqrt(Sigma)          the norm of the gradient AdamW applies (after the 1/world average)
+ *   clip[1] = coef = min(1, max_norm / (norm + 1e-6))  exactly 1 when max_norm = +inf (measure only); NaN norm -> NaN, infinite norm -> 0
+ *   clip[2] = skip = 1 when skip_nonfinite != 0 and norm is not finite, else 0
+ *   clip[3] += skip                                    running count of skipped steps (read, incremented, written here)
+ * max_norm > 0 (NaN rejected).  n = 0: norm 0, coef 1, skip 0. */
+int ytvln_grad_clip_coef(const float* partials, int64_t n, float grad_scale, float max_norm, int skip_nonfinite, float* clip,
+                         void* stream);
+/* ytvln_adamw_f32 / _bf16copy / _gbf16 in one entry (g_dtype selects the gradient operand, p_bf16 may be NULL) reading `clip`: with
+ * clip[2] != 0 the launch leaves p, m, v and p_bf16 untouched; otherwise g is scaled by grad_scale * clip[1].  With clip[1] = 1 and clip[2] = 0
+ * it is bit-identical to those three. */
+int ytvln_adamw_clip(float* p, const void* g, int g_dtype, float* m, float* v, uint16_t* p_bf16, const void* chunks, int nchunks,
+                     const float* hyper, float grad_scale, const float* clip, void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI ------------------------------------------------------------------------
  * Replaces DistributedDataParallel over NCCL (utils/distributed.py:63-104: init_process_group("nccl") + DDP's bucketed all-reduce).

@@ -5,7 +5,9 @@
 // skips (grad is None: never-used heads, vilbert_init/optimization.py:143-144) are simply absent from the chunk table,
 // so they receive neither state nor decay.  Hyper-parameters live in device memory so a captured hipGraph can be
 // replayed while the host updates the learning rate.  The data-parallel bf16 gradient exchange adds a form that reads bf16 gradient sums
-// (26 bytes per parameter) and the pack pass that rounds the fp32 arena into its send buffer.
+// (26 bytes per parameter) and the pack pass that rounds the fp32 arena into its send buffer.  Opt-in global gradient-norm clipping adds one
+// streaming pass over the gradients (grad_sumsq_kernel: +4 bytes per parameter, +2 over the bf16 sums), one single-workgroup reduction
+// (grad_clip_coef_kernel) and an instantiation of the update that reads its gradient scale from the four-float record that reduction wrote.
 #include "common.h"
 
 namespace ytvln {
@@ -48,10 +50,21 @@ __device__ __forceinline__ void adam1_tail(float& p, float g, float& m, float& v
     if (lrwd != 0.f) p = __builtin_fmaf(-lrwd, p, p);
 }
 
-template <typename GT>
+// CLIP (global gradient-norm clipping, ytvln_adamw_clip): `clip` is the device record {norm, coef, skip, skipped} of grad_clip_coef_kernel.
+// skip != 0: the whole launch returns before touching p, m, v or the bf16 copy; otherwise the gradient scale is gscale * coef.  A template
+// parameter, not a run-time branch: the CLIP = false instantiations never read `clip` and keep the instruction streams they had before it existed.
+// With coef == 1 the product is `gscale` itself and everything after it is the same source: the compiler contracts body and tail as in the
+// CLIP = false instantiations (the floating-point instruction mix differs by that one multiply), so the update equals theirs bit for bit on
+// every element, tails included (tests/test_grad_clip_gpu.py pins it).
+template <typename GT, bool CLIP = false>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ P, const GT* __restrict__ G, float* __restrict__ Mo,
                                                     float* __restrict__ Vo, const AdamChunk* __restrict__ chunks,
-                                                    const float* __restrict__ hyper, float gscale, uint16_t* __restrict__ PB) {
+                                                    const float* __restrict__ hyper, float gscale, uint16_t* __restrict__ PB,
+                                                    const float* __restrict__ clip) {
+    if constexpr (CLIP) {
+        if (clip[2] != 0.f) return;
+        gscale *= clip[1];
+    }
     const AdamChunk c = chunks[blockIdx.x];
     const float b1 = hyper[0], b2 = hyper[1], eps = hyper[2], ss = hyper[3], lr = hyper[4];
     const float lrwd = lr * c.wd;
@@ -96,6 +109,63 @@ __global__ __launch_bounds__(256) void grad_pack_bf16_kernel(const float* __rest
     for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) o[i] = (uint16_t)bf16_bits(g[i]);
 }
 
+// Sum of squares of the gradient the update will read (the fp32 arena, or the bf16 sums of the bf16 exchange at the same offsets) over an
+// AdamW chunk table: one workgroup per record, one fp32 partial per record, no atomics.  A thread issues its vector loads eight at a time
+// and adds the squares into ONE accumulator in element order (a record of 16384 elements: 64 serial terms per thread), then the workgroup
+// sums in a fixed tree: six butterfly levels inside each wave, two across the four waves.  Every order is fixed, so a partial is the
+// same bits on every run.  Read-only: 4 bytes per element (2 for bf16).
+template <typename GT>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const GT* __restrict__ G, const AdamChunk* __restrict__ chunks,
+                                                         float* __restrict__ partials) {
+    __shared__ float wsum[4];
+    const AdamChunk c = chunks[blockIdx.x];
+    const GT* g = G + c.off;
+    const int64_t n4 = ((c.off & 3) == 0) ? (c.len >> 2) : 0;
+    float acc = 0.f;
+    for (int64_t i = threadIdx.x; i < n4; i += 8 * 256) {
+        float4 x[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = (i + k * 256 < n4) ? load_g4(g, i + k * 256) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            acc = __builtin_fmaf(x[k].x, x[k].x, acc); acc = __builtin_fmaf(x[k].y, x[k].y, acc);
+            acc = __builtin_fmaf(x[k].z, x[k].z, acc); acc = __builtin_fmaf(x[k].w, x[k].w, acc);
+        }
+    }
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) { const float x = load_g1(g, i); acc = __builtin_fmaf(x, x, acc); }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// One workgroup: Sigma = the sum of all n partials in fp64 (thread t takes t, t + 256, ... in order, then a fixed halving tree through LDS),
+// and the record the clip-aware update reads.  The formula and the non-finite behaviour are torch.nn.utils.clip_grad_norm_'s
+// (error_if_nonfinite = False): coef = min(1, max_norm / (norm + 1e-6)) in fp32, a NaN norm gives a NaN coefficient, an infinite one 0;
+// max_norm = +inf means "measure, do not clip": coef is exactly 1.  clip[3] counts the skipped steps (exact in fp32 up to 2^24).
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ partials, int64_t n, float gscale, float max_norm,
+                                                             int skip_nonfinite, float* __restrict__ clip) {
+    __shared__ double s[256];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) acc += (double)partials[i];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)((double)gscale * sqrt(s[0]));
+        float coef = 1.0f;
+        if (max_norm < INFINITY) {
+            coef = max_norm / (norm + 1e-6f);
+            if (coef > 1.0f) coef = 1.0f;          // (a NaN stays a NaN, as torch.clamp(max=1) leaves it)
+        }
+        const bool skip = skip_nonfinite && !(fabsf(norm) < INFINITY);
+        *reinterpret_cast<float4*>(clip) = make_float4(norm, coef, skip ? 1.0f : 0.0f, clip[3] + (skip ? 1.0f : 0.0f));
+    }
+}
+
 }  // namespace ytvln
 
 using namespace ytvln;
@@ -106,7 +176,7 @@ extern "C" int ytvln_adamw_f32(float* p, const float* g, float* m, float* v, con
     YT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adamw: arenas must be 16-byte aligned");
     if (nchunks <= 0) return 0;
     hipLaunchKernelGGL(adamw_kernel<float>, dim3(nchunks), dim3(256), 0, as_stream(stream), p, g, m, v,
-                       reinterpret_cast<const AdamChunk*>(chunks), hyper, grad_scale, (uint16_t*)nullptr);
+                       reinterpret_cast<const AdamChunk*>(chunks), hyper, grad_scale, (uint16_t*)nullptr, (const float*)nullptr);
     YT_LAUNCH_CHECK("adamw");
     return 0;
 }
@@ -117,7 +187,7 @@ extern "C" int ytvln_adamw_f32_bf16copy(float* p, const float* g, float* m, floa
     YT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)p_bf16) & 15) == 0, "adamw_bf16copy: arenas must be 16-byte aligned");
     if (nchunks <= 0) return 0;
     hipLaunchKernelGGL(adamw_kernel<float>, dim3(nchunks), dim3(256), 0, as_stream(stream), p, g, m, v,
-                       reinterpret_cast<const AdamChunk*>(chunks), hyper, grad_scale, p_bf16);
+                       reinterpret_cast<const AdamChunk*>(chunks), hyper, grad_scale, p_bf16, (const float*)nullptr);
     YT_LAUNCH_CHECK("adamw_bf16copy");
     return 0;
 }
@@ -129,7 +199,7 @@ extern "C" int ytvln_adamw_f32_gbf16(float* p, const uint16_t* g_bf16, float* m,
                "adamw_gbf16: arenas must be 16-byte aligned");
     if (nchunks <= 0) return 0;
     hipLaunchKernelGGL(adamw_kernel<uint16_t>, dim3(nchunks), dim3(256), 0, as_stream(stream), p, g_bf16, m, v,
-                       reinterpret_cast<const AdamChunk*>(chunks), hyper, grad_scale, p_bf16);
+                       reinterpret_cast<const AdamChunk*>(chunks), hyper, grad_scale, p_bf16, (const float*)nullptr);
     YT_LAUNCH_CHECK("adamw_gbf16");
     return 0;
 }
@@ -141,5 +211,49 @@ extern "C" int ytvln_grad_pack_bf16(const float* g, uint16_t* g_bf16, const void
     hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), g, g_bf16,
                        reinterpret_cast<const AdamChunk*>(chunks));
     YT_LAUNCH_CHECK("grad_pack_bf16");
+    return 0;
+}
+
+extern "C" int ytvln_grad_sumsq(const void* g, int dtype, const void* chunks, int nchunks, float* partials, void* stream) {
+    YT_REQUIRE(g && chunks && partials, "grad_sumsq: null pointer");
+    YT_REQUIRE(dtype == YTVLN_DT_F32 || dtype == YTVLN_DT_BF16, "grad_sumsq: dtype %d (fp32 or bf16 gradients only)", dtype);
+    YT_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)partials & 3) == 0, "grad_sumsq: the gradient arena must be 16-byte aligned");
+    if (nchunks <= 0) return 0;
+    const AdamChunk* ch = reinterpret_cast<const AdamChunk*>(chunks);
+    if (dtype == YTVLN_DT_F32)
+        hipLaunchKernelGGL(grad_sumsq_kernel<float>, dim3(nchunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(g), ch, partials);
+    else
+        hipLaunchKernelGGL(grad_sumsq_kernel<uint16_t>, dim3(nchunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const uint16_t*>(g), ch,
+                           partials);
+    YT_LAUNCH_CHECK("grad_sumsq");
+    return 0;
+}
+
+extern "C" int ytvln_grad_clip_coef(const float* partials, int64_t n, float grad_scale, float max_norm, int skip_nonfinite, float* clip,
+                                    void* stream) {
+    YT_REQUIRE(clip && (partials || n == 0), "grad_clip_coef: null pointer");
+    YT_REQUIRE(n >= 0, "grad_clip_coef: n = %lld", (long long)n);
+    YT_REQUIRE(((uintptr_t)clip & 15) == 0, "grad_clip_coef: the clip record must be 16-byte aligned");
+    YT_REQUIRE(max_norm > 0.f, "grad_clip_coef: max_norm must be > 0 (+inf: no clipping), got %g", (double)max_norm);      // (false for a NaN)
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials, n, grad_scale, max_norm, skip_nonfinite, clip);
+    YT_LAUNCH_CHECK("grad_clip_coef");
+    return 0;
+}
+
+extern "C" int ytvln_adamw_clip(float* p, const void* g, int g_dtype, float* m, float* v, uint16_t* p_bf16, const void* chunks, int nchunks,
+                                const float* hyper, float grad_scale, const float* clip, void* stream) {
+    YT_REQUIRE(p && g && m && v && chunks && hyper && clip, "adamw_clip: null pointer");
+    YT_REQUIRE(g_dtype == YTVLN_DT_F32 || g_dtype == YTVLN_DT_BF16, "adamw_clip: g_dtype %d (fp32 or bf16 gradients only)", g_dtype);
+    YT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)p_bf16) & 15) == 0,
+               "adamw_clip: arenas must be 16-byte aligned");
+    if (nchunks <= 0) return 0;
+    const AdamChunk* ch = reinterpret_cast<const AdamChunk*>(chunks);
+    if (g_dtype == YTVLN_DT_F32)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(adamw_kernel<float, true>), dim3(nchunks), dim3(256), 0, as_stream(stream), p,
+                           reinterpret_cast<const float*>(g), m, v, ch, hyper, grad_scale, p_bf16, clip);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(adamw_kernel<uint16_t, true>), dim3(nchunks), dim3(256), 0, as_stream(stream), p,
+                           reinterpret_cast<const uint16_t*>(g), m, v, ch, hyper, grad_scale, p_bf16, clip);
+    YT_LAUNCH_CHECK("adamw_clip");
     return 0;
 }

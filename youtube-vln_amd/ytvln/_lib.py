@@ -84,6 +84,9 @@ SIGNATURES = {
     "ytvln_adamw_f32_bf16copy": [P, P, P, P, P, P, I32, P, F32, P],
     "ytvln_adamw_f32_gbf16": [P, P, P, P, P, P, I32, P, F32, P],
     "ytvln_grad_pack_bf16": [P, P, P, I32, P],
+    "ytvln_grad_sumsq": [P, I32, P, I32, P, P],
+    "ytvln_grad_clip_coef": [P, I64, F32, F32, I32, P, P],
+    "ytvln_adamw_clip": [P, P, I32, P, P, P, P, I32, P, F32, P, P],
     "ytvln_ln_fwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, I64, P],
     "ytvln_ln_bwd_blocks": [I64],
     "ytvln_ln_bwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],

@@ -548,6 +548,12 @@ class GraphedTrainStep:
     The host enqueues a handful of graph launches and RCCL groups per step instead of ~1500 kernels, so N processes do not compete for host
     cores; no watchdog thread, no hidden stream.
 
+    With gradient clipping on (AdamW.max_grad_norm / skip_nonfinite, fixed at capture) the norm is taken over what the update reads, after the
+    exchange: split and single record the three launches (sum of squares, coefficient, clip-aware AdamW) where the update sits.  Phased takes
+    each group's sum of squares on the communication stream right behind that group's all-reduce, under the following backward phases, and
+    defers EVERY update until the last group's partials exist (a global norm needs all of them): the exchange still overlaps, the update no
+    longer does.  With clipping off phased is unchanged.
+
     With the bf16 exchange of the wrapped DataParallel (`grad_dtype`) every form packs what it exchanges into the optimizer's bf16 buffer
     right before the collective (split: at the end of graph A; single: inside the graph; phased: per group on the communication stream),
     all-reduces the bf16 slices and runs AdamW on the bf16 sums.
@@ -586,6 +592,8 @@ class GraphedTrainStep:
             optimizer.bf16_arena()          # the one-time cast of the whole weight arena happens here, eagerly: not recorded into a graph
         if self.bf16:
             optimizer.grad_bf16()           # the exchange buffer is allocated eagerly, outside the graphs' pools
+        if hasattr(optimizer, "clip_settings") and optimizer.clip_settings() is not None:
+            optimizer.clip_buffers()        # gradient clipping on: its partials and its record, eagerly as well
         torch.cuda.synchronize()
         flat = optimizer.flat_grad()
         # the buffer the collectives work on: the fp32 arena, or its bf16 copy (same offsets; slices stay element ranges)
@@ -792,6 +800,9 @@ class GraphedTrainStep:
             self.opt.prepare_replay()                   # hyper-parameters of this step: uploaded before the first per-group update
             tables = self.opt.group_tables(self._group_slices, owner=self)
             overlap = self.comm is not None or not self.exchange          # (torch.distributed data plane: everything in stream order)
+            # gradient clipping: per group only the sum of squares; the coefficient and every update wait for the last group's partials
+            clip = hasattr(self.opt, "clip_settings") and self.opt.clip_settings() is not None
+            slot = 0
             for k, g in enumerate(self.graphs):
                 g.replay()
                 if not self._group_slices[k]:
@@ -801,7 +812,10 @@ class GraphedTrainStep:
                         self.opt.pack_grads(tables[k])
                     for lo, hi in self._group_slices[k]:
                         dist.all_reduce(xbuf[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
-                    self.opt.launch_tables(tables[k])
+                    if clip:
+                        slot = self.opt.sumsq_tables(tables[k], slot)
+                    else:
+                        self.opt.launch_tables(tables[k])
                     continue
                 self._events[k].record(cur)
                 self._comm_stream.wait_event(self._events[k])
@@ -816,7 +830,15 @@ class GraphedTrainStep:
                     e1.record(self._comm_stream)
                     self._prof_events = (e0, e1)
                 with torch.cuda.stream(self._comm_stream):
-                    self.opt.launch_tables(tables[k])
+                    if clip:
+                        slot = self.opt.sumsq_tables(tables[k], slot)
+                    else:
+                        self.opt.launch_tables(tables[k])
+            if clip:
+                with torch.cuda.stream(self._comm_stream) if overlap else contextlib.nullcontext():
+                    self.opt.clip_coef(slot)
+                    for t in tables:
+                        self.opt.launch_tables(t)
             if overlap:
                 cur.wait_stream(self._comm_stream)
             self.opt.finish_group_step()

@@ -1752,3 +1752,44 @@ def grad_pack_bf16(g: Tensor, g_bf16: Tensor, chunks: Tensor, nchunks: int):
     _check(g, "g")
     _check(g_bf16, "g_bf16", torch.bfloat16)
     call("ytvln_grad_pack_bf16", _ptr(g), g_bf16.data_ptr(), chunks.data_ptr(), int(nchunks), _stream())
+
+
+def _grad_dtype(g: Tensor) -> int:
+    if g.dtype == torch.float32:
+        return _lib.DT_F32
+    if g.dtype == torch.bfloat16:
+        return _lib.DT_BF16
+    raise RuntimeError(f"gradients must be float32 or bfloat16, got {g.dtype}")
+
+
+def grad_sumsq(g: Tensor, chunks: Tensor, nchunks: int, partials: Tensor):
+    """partials[i] = sum(g[o:o+len] ** 2) for record i of an AdamW chunk table (`g`: the fp32 gradient arena or the bf16 exchange buffer),
+    one float per record, on the current stream.  `partials` is a float32 view with room for `nchunks` values."""
+    dt = _grad_dtype(g)
+    _check(g, "g", g.dtype)
+    _check(partials, "partials")
+    if partials.numel() < int(nchunks):
+        raise RuntimeError(f"grad_sumsq: {int(nchunks)} records, room for {partials.numel()} partials")
+    call("ytvln_grad_sumsq", g.data_ptr(), dt, chunks.data_ptr(), int(nchunks), _ptr(partials), _stream())
+
+
+def grad_clip_coef(partials: Tensor, n: int, grad_scale: float, max_norm: float, skip_nonfinite: bool, clip: Tensor):
+    """clip = [norm, coef, skip, skipped steps] from the first `n` partials (include/ytvln.h: ytvln_grad_clip_coef), on the current stream.
+    `max_norm` = inf measures without clipping."""
+    _check(partials, "partials")
+    _check(clip, "clip")
+    if clip.numel() != 4 or partials.numel() < int(n):
+        raise RuntimeError("grad_clip_coef: clip is a record of 4 floats and partials must hold n values")
+    call("ytvln_grad_clip_coef", _ptr(partials), int(n), float(grad_scale), float(max_norm), int(bool(skip_nonfinite)), _ptr(clip), _stream())
+
+
+def adamw_step_clip(p: Tensor, g: Tensor, m: Tensor, v: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor, clip: Tensor,
+                    grad_scale: float = 1.0, p_bf16: Optional[Tensor] = None):
+    """adamw_step / adamw_step_gbf16 (by the dtype of `g`) with the gradient scale grad_scale * clip[1] read from the device record of
+    grad_clip_coef; a no-op when clip[2] != 0."""
+    for t, nme in ((p, "p"), (m, "m"), (v, "v"), (hyper, "hyper"), (clip, "clip")):
+        _check(t, nme)
+    dt = _grad_dtype(g)
+    _check(g, "g", g.dtype)
+    call("ytvln_adamw_clip", _ptr(p), g.data_ptr(), dt, _ptr(m), _ptr(v), None if p_bf16 is None else p_bf16.data_ptr(),
+         chunks.data_ptr(), int(nchunks), _ptr(hyper), float(grad_scale), _ptr(clip), _stream())

@@ -7,10 +7,14 @@ the update, tensors without a gradient skipped entirely).  Execution differs: on
 received a gradient are moved into one flat fp32 arena (their `.data` / `.grad` become views), moments live in two more
 arenas, and a whole step is one HIP kernel launch per (param-group, step-count) class instead of ~8 ATen kernels per
 tensor x 541 tensors.  The flat gradient arena is also what the data-parallel all-reduce buckets (ytvln/distributed.py).
+
+Beyond the reference (it has no gradient clipping): two plain attributes, `optimizer.max_grad_norm` and `optimizer.skip_nonfinite`, bound
+the global gradient norm inside the step -- see the `AdamW` docstring.
 """
 from __future__ import annotations
 
 import math
+import numbers
 import struct
 from typing import Dict, List
 
@@ -91,6 +95,29 @@ class WarmupCosineWithHardRestartsSchedule(LambdaLR):
 
 
 class AdamW(Optimizer):
+    """The reference's AdamW, fused (module docstring), plus opt-in global gradient-norm clipping.
+
+    max_grad_norm (attribute, default None): a number > 0 bounds the global L2 norm of the gradient the update applies -- after the
+        data-parallel exchange and its 1/world average, over the bf16 sums when the exchange is bf16 -- with
+        torch.nn.utils.clip_grad_norm_'s formula, coef = min(1, max_norm / (norm + 1e-6)); float("inf") measures the norm without clipping.
+    skip_nonfinite (attribute, default False): a step whose gradient norm is inf or NaN leaves parameters, moments and the bf16 weight copy
+        untouched and is counted.  Without it a non-finite norm behaves as in torch (error_if_nonfinite=False): the coefficient becomes 0 or
+        NaN and goes into the update.
+    Both are plain attributes: not constructor arguments, not in `param_groups` / `defaults`, not in `state_dict()` (checkpoints stay
+    interchangeable with the reference).  With both at their defaults a step launches exactly the kernels it always launched.  With either
+    set, every step -- eager, while capturing, on replay -- runs, between the gradient exchange and the update: ytvln_grad_sumsq over
+    every launch class, one ytvln_grad_clip_coef, then ytvln_adamw_clip per class; no host synchronisation, no atomics, fixed summation
+    orders.  Invalid values (<= 0, NaN, not a number) raise ValueError when the step is taken.
+
+    The decision to skip is taken on the device: the host cannot know it without a sync, so on a skipped step `state[p]["step"]` (the
+    bias-correction count) and an LR scheduler still advance.  `grad_norm()` is a 0-d device view of the last step's norm (no sync);
+    `skipped_steps()` reads the count of skipped steps back (synchronises); the count restarts when the arenas are rebuilt
+    (load_state_dict, a changed parameter set).
+
+    A captured step bakes both settings into the graph: changing either afterwards makes the next `prepare_replay()` raise; capture the
+    step again.  Capturing with the feature on needs its two small device buffers, which the first eager step with the feature on (or
+    `clip_buffers()`) allocates."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
@@ -107,6 +134,9 @@ class AdamW(Optimizer):
         # torch.bfloat16 (set by data-parallel wrappers with the bf16 exchange): the update reads the bf16 exchange buffer (grad_bf16()),
         # not the fp32 arena.  Local accumulation stays fp32 either way.
         self.exchange_dtype = torch.float32
+        self.max_grad_norm = None   # global gradient-norm clipping (class docstring); plain attributes, never part of state_dict()
+        self.skip_nonfinite = False
+        self._captured_clip = False  # the clipping settings recorded into the last captured step (False: nothing captured yet)
 
     # ---- arena management -----------------------------------------------------------------------------------------
     def _members(self):
@@ -147,7 +177,7 @@ class AdamW(Optimizer):
                 p.grad = flat["g"][o:o + n].view(p.shape)
                 st["exp_avg"] = flat["m"][o:o + n].view(p.shape)
                 st["exp_avg_sq"] = flat["v"][o:o + n].view(p.shape)
-        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None)
+        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None, partials=None, clip=None)
         self._launch = None
         del old
         # let the weight-gradient GEMMs write straight into the gradient arena and the packed projections alias the
@@ -206,9 +236,86 @@ class AdamW(Optimizer):
         for _, table, n in tables:
             ops.grad_pack_bf16(self._arena["g"], gb, table, n)
 
-    def _update(self, table, n, hyper):
+    # ---- global gradient-norm clipping ------------------------------------------------------------------------------
+    def clip_settings(self):
+        """None with the feature off, else (max_norm as a float -- inf: measure only --, skip_nonfinite).  Raises ValueError for a
+        max_grad_norm that is not a number > 0."""
+        mx = self.max_grad_norm
+        if mx is None and not self.skip_nonfinite:
+            return None
+        if mx is None:
+            return math.inf, True
+        if isinstance(mx, bool) or not isinstance(mx, numbers.Real):
+            raise ValueError(f"max_grad_norm must be None or a number > 0, got {mx!r}")
+        mx = float(mx)
+        if not mx > 0.0:          # (also a NaN)
+            raise ValueError(f"max_grad_norm must be > 0, got {mx!r}")
+        return mx, bool(self.skip_nonfinite)
+
+    def clip_buffers(self):
+        """(partials, clip): one fp32 partial per CHUNK record of the arena and the record [norm, coef, skip, skipped steps] the kernels
+        exchange.  Allocated on first use -- only with the feature on -- and dropped with the arena; not part of state_dict.  None before
+        the arena exists."""
+        a = self._arena
+        if a is None:
+            return None
+        if a["clip"] is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("gradient clipping was switched on after the last eager step: take one eager step with it on (or call "
+                                   "clip_buffers()) before capturing, so that its buffers do not live in a graph's pool")
+            n = sum((numel + CHUNK - 1) // CHUNK for _, numel in a["index"].values())
+            a["partials"] = torch.zeros(n, dtype=torch.float32, device=a["g"].device)
+            a["clip"] = torch.zeros(4, dtype=torch.float32, device=a["g"].device)
+        return a["partials"], a["clip"]
+
+    def _grad_operand(self):
+        """The gradient the update reads: the fp32 arena, or the bf16 sums of the bf16 exchange."""
         a = self._arena
         if self.exchange_dtype == torch.bfloat16:
+            if a["gb"] is None:
+                raise RuntimeError("bf16 gradient exchange: the update would read a bf16 buffer nothing was packed into")
+            return a["gb"]
+        return a["g"]
+
+    def sumsq_tables(self, tables, slot):
+        """ytvln_grad_sumsq over `tables` = [(launch class index, chunk table, number of chunks)] on the current stream, into the partials
+        from `slot` on; returns the next free slot."""
+        partials, _ = self.clip_buffers()
+        g = self._grad_operand()
+        for _, table, n in tables:
+            if slot + n > partials.numel():
+                raise RuntimeError("gradient clipping: more chunk records than the arena has")
+            ops.grad_sumsq(g, table, n, partials[slot:slot + n])
+            slot += n
+        return slot
+
+    def clip_coef(self, n):
+        """ytvln_grad_clip_coef over the first `n` partials on the current stream: from here on the clip record is this step's."""
+        max_norm, skip = self.clip_settings()
+        partials, clip = self.clip_buffers()
+        ops.grad_clip_coef(partials, n, self.grad_scale, max_norm, skip, clip)
+
+    def grad_norm(self):
+        """0-d device tensor: the global L2 norm of the gradient the last step applied (before clipping, after the 1/world average).  A
+        view of the clip record -- no synchronisation; later steps overwrite it."""
+        a = self._arena
+        if a is None or a["clip"] is None:
+            raise RuntimeError("grad_norm(): no step has been taken with max_grad_norm / skip_nonfinite set")
+        return a["clip"][0]
+
+    def skipped_steps(self) -> int:
+        """Steps skipped for a non-finite gradient norm since the arenas were built.  Reads a device counter: SYNCHRONISES."""
+        a = self._arena
+        if a is None or a["clip"] is None:
+            return 0
+        return int(a["clip"][3].item())
+
+    def _update(self, table, n, hyper):
+        a = self._arena
+        if self.clip_settings() is not None:
+            ops.adamw_step_clip(a["p"], self._grad_operand(), a["m"], a["v"], table, n, hyper, self.clip_buffers()[1], self.grad_scale,
+                                p_bf16=a["pb"])
+        elif self.exchange_dtype == torch.bfloat16:
             if a["gb"] is None:
                 raise RuntimeError("bf16 gradient exchange: the update would read a bf16 buffer nothing was packed into")
             ops.adamw_step_gbf16(a["p"], a["gb"], a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
@@ -297,6 +404,10 @@ class AdamW(Optimizer):
                 self.state[p]["step"] = t
 
     def _launch_kernels(self):
+        if self.clip_settings() is not None:      # norm of what the update reads -> coefficient -> clip-aware update, all in stream order
+            self.clip_coef(self.sumsq_tables([(ci, c["table"], c["n"]) for ci, c in enumerate(self._launch)], 0))
+        if torch.cuda.is_current_stream_capturing():
+            self._captured_clip = self.clip_settings()
         for c in self._launch:
             self._update(c["table"], c["n"], c["hyper"])
 
@@ -306,6 +417,7 @@ class AdamW(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self.clip_settings()              # invalid max_grad_norm: ValueError before anything is exchanged, launched or recorded
         if torch.cuda.is_current_stream_capturing():
             # inside a hipGraph capture of a whole training step: only the device work is recorded; the caller uploads the
             # hyper-parameters eagerly before every replay (`prepare_replay()`).  The arena must already exist.
@@ -426,7 +538,11 @@ class AdamW(Optimizer):
         return None if self._arena is None else self._arena["g"]
 
     def prepare_replay(self):
-        """Call before each replay of a captured training step (after scheduler.step() set the new learning rate)."""
+        """Call before each replay of a captured training step (after scheduler.step() set the new learning rate).  The captured step
+        carries the clipping settings it was recorded with: raises if max_grad_norm / skip_nonfinite changed since."""
+        if self._captured_clip is not False and self.clip_settings() != self._captured_clip:
+            raise RuntimeError(f"max_grad_norm / skip_nonfinite changed since the step was captured (captured {self._captured_clip}, now "
+                               f"{self.clip_settings()}): the graph holds the old launches -- capture the step again")
         self._upload_hyper()
 
     def zero_grad(self, set_to_none: bool = True):

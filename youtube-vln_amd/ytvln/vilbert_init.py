@@ -62,6 +62,9 @@ def restore_checkpoint(path, model, optimizer, scheduler, logger=None) -> int:
 def get_optimization(args, model, train_data_loader_length, logger):
     """-> (optimizer, scheduler, model, start_epoch), the reference's signature and return order."""
     optimizer = AdamW(grouped_parameters(model, args.weight_decay), lr=args.learning_rate)
+    # global gradient-norm clipping (beyond the reference; ytvln.optimization.AdamW): argument objects without the fields leave it off
+    optimizer.max_grad_norm = getattr(args, "max_grad_norm", None)
+    optimizer.skip_nonfinite = bool(getattr(args, "skip_nonfinite_grads", False))
     scheduler = build_scheduler(args, optimizer, train_data_loader_length)
     start_epoch = 0
     if getattr(args, "resume", False):
