@@ -419,6 +419,28 @@ int ytvln_grad_clip_coef(const float* partials, int64_t n, float grad_scale, flo
  * it is bit-identical to those three. */
 int ytvln_adamw_clip(float* p, const void* g, int g_dtype, float* m, float* v, uint16_t* p_bf16, const void* chunks, int nchunks,
                      const float* hyper, float grad_scale, const float* clip, void* stream);
+/* LAMB layer-wise trust ratio (You et al., 2020; the reference has none): the AdamW direction rescaled per parameter tensor, three launches
+ * per chunk table: ytvln_lamb_stage1 -> ytvln_lamb_trust -> ytvln_lamb_stage2.  With g = g_in * grad_scale (* clip[1] with a clip record):
+ *   m = beta1 m + (1-beta1) g;  v = beta2 v + (1-beta2) g^2;  r = hyper[5] * m / (sqrt(v) + eps) + wd * p    (decay INSIDE the direction)
+ *   trust(tensor) = ||p|| / ||r|| when wd != 0 and both norms are finite and > 0, else 1;   p -= lr * trust * r
+ * hyper[5] is the bias correction b = sqrt(1-beta2^t)/(1-beta1^t) (1 without it), so hyper[3] = lr * b as for ytvln_adamw_f32.  The norms
+ * run over whole tensors.  No atomics, every summation order fixed: results are reproducible bit for bit.  `clip` is the record of
+ * ytvln_grad_clip_coef or NULL (no clipping); with clip[2] != 0 all three launches return before writing anything.
+ *   stage 1: reads p, g, m, v; writes m, v and, for record i of the table, partials[2i] = sum p^2, partials[2i+1] = sum r^2 (fp32, one
+ * workgroup per record; r is not stored).  g_dtype: YTVLN_DT_F32 or YTVLN_DT_BF16, nothing else.  Arenas 16-byte, partials 8-byte aligned.
+ * 24 bytes per parameter. */
+int ytvln_lamb_stage1(const float* p, const void* g, int g_dtype, float* m, float* v, const void* chunks, int nchunks, const float* hyper,
+                      float grad_scale, const float* clip, float* partials, void* stream);
+/* One wave per tensor of the table.  The records of a tensor are contiguous in the table: tensor_first[t] is the first record of the
+ * table's t-th tensor (ntensors + 1 entries, ascending), rec_tensor[i] the index of record i's tensor in the trust / report buffers.
+ * Sums the tensor's partials in fp64 and writes trust[k] and the row report[4k .. 4k+3] = {||p||, ||r||, trust, 0} (16-byte aligned),
+ * k = rec_tensor[tensor_first[t]]; wd is read from the tensor's first record. */
+int ytvln_lamb_trust(const float* partials, const void* chunks, const int32_t* tensor_first, const int32_t* rec_tensor, int ntensors,
+                     float* trust, float* report, const float* clip, void* stream);
+/* stage 2: reads p and the m, v stage 1 stored, recomputes r with stage 1's expression (bit-identical), applies
+ * p -= lr * trust[rec_tensor[i]] * r and writes p, and bf16(p) into p_bf16 when that is not NULL.  16 bytes per parameter, 18 with the copy. */
+int ytvln_lamb_stage2(float* p, const float* m, const float* v, uint16_t* p_bf16, const void* chunks, int nchunks, const float* hyper,
+                      const float* trust, const int32_t* rec_tensor, const float* clip, void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI ------------------------------------------------------------------------
  * Replaces DistributedDataParallel over NCCL (utils/distributed.py:63-104: init_process_group("nccl") + DDP's bucketed all-reduce).

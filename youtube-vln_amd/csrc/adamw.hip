@@ -8,6 +8,8 @@
 // (26 bytes per parameter) and the pack pass that rounds the fp32 arena into its send buffer.  Opt-in global gradient-norm clipping adds one
 // streaming pass over the gradients (grad_sumsq_kernel: +4 bytes per parameter, +2 over the bf16 sums), one single-workgroup reduction
 // (grad_clip_coef_kernel) and an instantiation of the update that reads its gradient scale from the four-float record that reduction wrote.
+// Opt-in LAMB layer-wise trust ratio splits the update into two streaming passes around a per-tensor reduction (lamb_stage1_kernel: 24 bytes
+// per parameter, lamb_trust_kernel, lamb_stage2_kernel: 16, 18 with the bf16 copy): 40 bytes per parameter against 28.
 #include "common.h"
 
 namespace ytvln {
@@ -166,6 +168,124 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __rest
     }
 }
 
+// ---- LAMB layer-wise trust ratio (You et al., 2020), opt-in: the AdamW direction rescaled per parameter tensor ----------------------------
+//   m, v: the moments of adamw_kernel;   r = b * m / (sqrt(v) + eps) + wd * p   (b: the bias correction, hyper[5]; decay INSIDE the direction)
+//   trust(tensor) = ||p|| / ||r|| when wd != 0 and both norms are finite and > 0, else 1;   p -= lr * trust * r
+// The norms run over whole tensors, so the update is two streaming passes with a per-tensor reduction between them.  r is not stored:
+// stage 2 recomputes it from the p it is about to overwrite and the m, v stage 1 stored (storing r would cost the same bytes and a scratch arena).
+// Every product-sum is an explicit fma, so the float4 body, the scalar tail and both stages round alike; no atomics, every summation
+// order fixed.  `clip` (may be NULL) is the record of grad_clip_coef_kernel: skip != 0 makes all three launches return before writing anything.
+__device__ __forceinline__ void lamb_moments(float g, float& m, float& v, float b1, float b2) {
+    m = __builtin_fmaf(1.0f - b1, g, m * b1);
+    v = __builtin_fmaf((1.0f - b2) * g, g, v * b2);
+}
+__device__ __forceinline__ float lamb_r(float p, float m, float v, float b, float eps, float wd) {
+    return __builtin_fmaf(b, m / (sqrtf(v) + eps), wd * p);
+}
+
+// Stage 1: one workgroup per chunk record.  Reads p, g, m, v; writes m, v and two fp32 partials per record, {sum p^2, sum r^2}, accumulated as
+// in grad_sumsq_kernel: one accumulator per thread and sum in element order (a record of 16384 elements: 64 serial terms), then six
+// butterfly levels inside each wave and two across the four waves.  24 bytes per parameter (22 with bf16 gradients).
+template <typename GT>
+__global__ __launch_bounds__(256) void lamb_stage1_kernel(const float* __restrict__ P, const GT* __restrict__ G, float* __restrict__ Mo,
+                                                          float* __restrict__ Vo, const AdamChunk* __restrict__ chunks,
+                                                          const float* __restrict__ hyper, float gscale, const float* __restrict__ clip,
+                                                          float2* __restrict__ partials) {
+    __shared__ float2 wsum[4];
+    if (clip) {
+        if (clip[2] != 0.f) return;
+        gscale *= clip[1];
+    }
+    const AdamChunk c = chunks[blockIdx.x];
+    const float b1 = hyper[0], b2 = hyper[1], eps = hyper[2], b = hyper[5], wd = c.wd;
+    const float* p = P + c.off; const GT* g = G + c.off; float* m = Mo + c.off; float* v = Vo + c.off;
+    const int64_t n4 = ((c.off & 3) == 0) ? (c.len >> 2) : 0;
+    float sp = 0.f, sr = 0.f;
+    for (int64_t i = threadIdx.x; i < n4; i += 256) {
+        const float4 pv = reinterpret_cast<const float4*>(p)[i];
+        float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        const float4 gv = load_g4(g, i);
+        lamb_moments(gv.x * gscale, mv.x, vv.x, b1, b2); lamb_moments(gv.y * gscale, mv.y, vv.y, b1, b2);
+        lamb_moments(gv.z * gscale, mv.z, vv.z, b1, b2); lamb_moments(gv.w * gscale, mv.w, vv.w, b1, b2);
+        reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
+        const float rx = lamb_r(pv.x, mv.x, vv.x, b, eps, wd), ry = lamb_r(pv.y, mv.y, vv.y, b, eps, wd);
+        const float rz = lamb_r(pv.z, mv.z, vv.z, b, eps, wd), rw = lamb_r(pv.w, mv.w, vv.w, b, eps, wd);
+        sp = __builtin_fmaf(pv.x, pv.x, sp); sp = __builtin_fmaf(pv.y, pv.y, sp); sp = __builtin_fmaf(pv.z, pv.z, sp); sp = __builtin_fmaf(pv.w, pv.w, sp);
+        sr = __builtin_fmaf(rx, rx, sr); sr = __builtin_fmaf(ry, ry, sr); sr = __builtin_fmaf(rz, rz, sr); sr = __builtin_fmaf(rw, rw, sr);
+    }
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) {
+        const float pi = p[i];
+        float mi = m[i], vi = v[i];
+        lamb_moments(load_g1(g, i) * gscale, mi, vi, b1, b2);
+        m[i] = mi; v[i] = vi;
+        const float r = lamb_r(pi, mi, vi, b, eps, wd);
+        sp = __builtin_fmaf(pi, pi, sp); sr = __builtin_fmaf(r, r, sr);
+    }
+    sp = wave_sum(sp); sr = wave_sum(sr);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = make_float2(sp, sr);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[blockIdx.x] = make_float2((wsum[0].x + wsum[1].x) + (wsum[2].x + wsum[3].x), (wsum[0].y + wsum[1].y) + (wsum[2].y + wsum[3].y));
+}
+
+// Trust: one wave per tensor of the class.  `first` holds the first record of each tensor (ntensors + 1 entries: the chunks of a tensor are
+// contiguous in a class's table), `rec_tensor` the tensor's index in the arena for every record.  Lane l adds the partials of records
+// first[t] + l, + 64, ... in order in fp64, then a fixed butterfly over the 64 lanes.  Writes trust[tensor] and the report row
+// {||p||, ||r||, trust, 0}.
+__global__ __launch_bounds__(64) void lamb_trust_kernel(const float2* __restrict__ partials, const AdamChunk* __restrict__ chunks,
+                                                        const int32_t* __restrict__ first, const int32_t* __restrict__ rec_tensor,
+                                                        float* __restrict__ trust, float4* __restrict__ report,
+                                                        const float* __restrict__ clip) {
+    if (clip && clip[2] != 0.f) return;
+    const int lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
+    if (hi <= lo) return;
+    double sp = 0.0, sr = 0.0;
+    for (int i = lo + (int)threadIdx.x; i < hi; i += 64) {
+        const float2 x = partials[i];
+        sp += (double)x.x; sr += (double)x.y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sr += __shfl_xor(sr, o, 64); }
+    if (threadIdx.x == 0) {
+        const double np = sqrt(sp), nr = sqrt(sr);
+        float t = 1.0f;
+        if (chunks[lo].wd != 0.f && np > 0.0 && np < (double)INFINITY && nr > 0.0 && nr < (double)INFINITY) t = (float)(np / nr);
+        const int k = rec_tensor[lo];
+        trust[k] = t;
+        report[k] = make_float4((float)np, (float)nr, t, 0.f);
+    }
+}
+
+// Stage 2: one workgroup per chunk record.  Reads p and the m, v of stage 1, recomputes r with stage 1's expression on the same values
+// (p is still the pre-update one), applies p -= lr * trust * r and writes p, and bf16(p) when PB != nullptr.  16 bytes per parameter, 18
+// with the copy.
+__global__ __launch_bounds__(256) void lamb_stage2_kernel(float* __restrict__ P, const float* __restrict__ Mo, const float* __restrict__ Vo,
+                                                          uint16_t* __restrict__ PB, const AdamChunk* __restrict__ chunks,
+                                                          const float* __restrict__ hyper, const float* __restrict__ trust,
+                                                          const int32_t* __restrict__ rec_tensor, const float* __restrict__ clip) {
+    if (clip && clip[2] != 0.f) return;
+    const AdamChunk c = chunks[blockIdx.x];
+    const float eps = hyper[2], lr = hyper[4], b = hyper[5], wd = c.wd;
+    const float nlt = -(lr * trust[rec_tensor[blockIdx.x]]);
+    float* p = P + c.off; const float* m = Mo + c.off; const float* v = Vo + c.off;
+    const int64_t n4 = ((c.off & 3) == 0) ? (c.len >> 2) : 0;
+    for (int64_t i = threadIdx.x; i < n4; i += 256) {
+        float4 pv = reinterpret_cast<float4*>(p)[i];
+        const float4 mv = reinterpret_cast<const float4*>(m)[i], vv = reinterpret_cast<const float4*>(v)[i];
+        pv.x = __builtin_fmaf(nlt, lamb_r(pv.x, mv.x, vv.x, b, eps, wd), pv.x);
+        pv.y = __builtin_fmaf(nlt, lamb_r(pv.y, mv.y, vv.y, b, eps, wd), pv.y);
+        pv.z = __builtin_fmaf(nlt, lamb_r(pv.z, mv.z, vv.z, b, eps, wd), pv.z);
+        pv.w = __builtin_fmaf(nlt, lamb_r(pv.w, mv.w, vv.w, b, eps, wd), pv.w);
+        reinterpret_cast<float4*>(p)[i] = pv;
+        if (PB) reinterpret_cast<uint2*>(PB + c.off)[i] = make_uint2(bf16_bits(pv.x) | (bf16_bits(pv.y) << 16), bf16_bits(pv.z) | (bf16_bits(pv.w) << 16));
+    }
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) {
+        const float pi = __builtin_fmaf(nlt, lamb_r(p[i], m[i], v[i], b, eps, wd), p[i]);
+        p[i] = pi;
+        if (PB) PB[c.off + i] = (uint16_t)bf16_bits(pi);
+    }
+}
+
 }  // namespace ytvln
 
 using namespace ytvln;
@@ -255,5 +375,49 @@ extern "C" int ytvln_adamw_clip(float* p, const void* g, int g_dtype, float* m, 
         hipLaunchKernelGGL(HIP_KERNEL_NAME(adamw_kernel<uint16_t, true>), dim3(nchunks), dim3(256), 0, as_stream(stream), p,
                            reinterpret_cast<const uint16_t*>(g), m, v, ch, hyper, grad_scale, p_bf16, clip);
     YT_LAUNCH_CHECK("adamw_clip");
+    return 0;
+}
+
+extern "C" int ytvln_lamb_stage1(const float* p, const void* g, int g_dtype, float* m, float* v, const void* chunks, int nchunks,
+                                 const float* hyper, float grad_scale, const float* clip, float* partials, void* stream) {
+    YT_REQUIRE(p && g && m && v && chunks && hyper && partials, "lamb_stage1: null pointer");
+    YT_REQUIRE(g_dtype == YTVLN_DT_F32 || g_dtype == YTVLN_DT_BF16, "lamb_stage1: g_dtype %d (fp32 or bf16 gradients only)", g_dtype);
+    YT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "lamb_stage1: arenas must be 16-byte aligned");
+    YT_REQUIRE(((uintptr_t)partials & 7) == 0, "lamb_stage1: the partials must be 8-byte aligned");
+    YT_REQUIRE(nchunks >= 0, "lamb_stage1: nchunks = %d", nchunks);
+    if (nchunks == 0) return 0;
+    const AdamChunk* ch = reinterpret_cast<const AdamChunk*>(chunks);
+    if (g_dtype == YTVLN_DT_F32)
+        hipLaunchKernelGGL(lamb_stage1_kernel<float>, dim3(nchunks), dim3(256), 0, as_stream(stream), p, reinterpret_cast<const float*>(g), m, v,
+                           ch, hyper, grad_scale, clip, reinterpret_cast<float2*>(partials));
+    else
+        hipLaunchKernelGGL(lamb_stage1_kernel<uint16_t>, dim3(nchunks), dim3(256), 0, as_stream(stream), p, reinterpret_cast<const uint16_t*>(g),
+                           m, v, ch, hyper, grad_scale, clip, reinterpret_cast<float2*>(partials));
+    YT_LAUNCH_CHECK("lamb_stage1");
+    return 0;
+}
+
+extern "C" int ytvln_lamb_trust(const float* partials, const void* chunks, const int32_t* tensor_first, const int32_t* rec_tensor,
+                                int ntensors, float* trust, float* report, const float* clip, void* stream) {
+    YT_REQUIRE(partials && chunks && tensor_first && rec_tensor && trust && report, "lamb_trust: null pointer");
+    YT_REQUIRE(((uintptr_t)partials & 7) == 0 && ((uintptr_t)report & 15) == 0,
+               "lamb_trust: the partials must be 8-byte and the report 16-byte aligned");
+    YT_REQUIRE(ntensors >= 0, "lamb_trust: ntensors = %d", ntensors);
+    if (ntensors == 0) return 0;
+    hipLaunchKernelGGL(lamb_trust_kernel, dim3(ntensors), dim3(64), 0, as_stream(stream), reinterpret_cast<const float2*>(partials),
+                       reinterpret_cast<const AdamChunk*>(chunks), tensor_first, rec_tensor, trust, reinterpret_cast<float4*>(report), clip);
+    YT_LAUNCH_CHECK("lamb_trust");
+    return 0;
+}
+
+extern "C" int ytvln_lamb_stage2(float* p, const float* m, const float* v, uint16_t* p_bf16, const void* chunks, int nchunks,
+                                 const float* hyper, const float* trust, const int32_t* rec_tensor, const float* clip, void* stream) {
+    YT_REQUIRE(p && m && v && chunks && hyper && trust && rec_tensor, "lamb_stage2: null pointer");
+    YT_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)p_bf16) & 15) == 0, "lamb_stage2: arenas must be 16-byte aligned");
+    YT_REQUIRE(nchunks >= 0, "lamb_stage2: nchunks = %d", nchunks);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(lamb_stage2_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), p, m, v, p_bf16,
+                       reinterpret_cast<const AdamChunk*>(chunks), hyper, trust, rec_tensor, clip);
+    YT_LAUNCH_CHECK("lamb_stage2");
     return 0;
 }

@@ -87,6 +87,9 @@ SIGNATURES = {
     "ytvln_grad_sumsq": [P, I32, P, I32, P, P],
     "ytvln_grad_clip_coef": [P, I64, F32, F32, I32, P, P],
     "ytvln_adamw_clip": [P, P, I32, P, P, P, P, I32, P, F32, P, P],
+    "ytvln_lamb_stage1": [P, P, I32, P, P, P, I32, P, F32, P, P, P],
+    "ytvln_lamb_trust": [P, P, P, P, I32, P, P, P, P],
+    "ytvln_lamb_stage2": [P, P, P, P, P, I32, P, P, P, P, P],
     "ytvln_ln_fwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, I64, P],
     "ytvln_ln_bwd_blocks": [I64],
     "ytvln_ln_bwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],

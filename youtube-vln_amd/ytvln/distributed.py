@@ -552,7 +552,9 @@ class GraphedTrainStep:
     exchange: split and single record the three launches (sum of squares, coefficient, clip-aware AdamW) where the update sits.  Phased takes
     each group's sum of squares on the communication stream right behind that group's all-reduce, under the following backward phases, and
     defers EVERY update until the last group's partials exist (a global norm needs all of them): the exchange still overlaps, the update no
-    longer does.  With clipping off phased is unchanged.
+    longer does.  With clipping off phased is unchanged.  The LAMB trust ratio (AdamW.trust_ratio) is fixed at capture in the same way;
+    split and single record its three launches per class where the update sits, and phased defers every update to the end of the step as
+    with clipping (the launches run over whole launch classes, which the gradient groups cut across).
 
     With the bf16 exchange of the wrapped DataParallel (`grad_dtype`) every form packs what it exchanges into the optimizer's bf16 buffer
     right before the collective (split: at the end of graph A; single: inside the graph; phased: per group on the communication stream),
@@ -594,6 +596,8 @@ class GraphedTrainStep:
             optimizer.grad_bf16()           # the exchange buffer is allocated eagerly, outside the graphs' pools
         if hasattr(optimizer, "clip_settings") and optimizer.clip_settings() is not None:
             optimizer.clip_buffers()        # gradient clipping on: its partials and its record, eagerly as well
+        if hasattr(optimizer, "lamb_setting") and optimizer.lamb_setting():
+            optimizer.lamb_buffers()        # LAMB trust ratio on: its partials, ratios and report rows
         torch.cuda.synchronize()
         flat = optimizer.flat_grad()
         # the buffer the collectives work on: the fp32 arena, or its bf16 copy (same offsets; slices stay element ranges)
@@ -802,6 +806,8 @@ class GraphedTrainStep:
             overlap = self.comm is not None or not self.exchange          # (torch.distributed data plane: everything in stream order)
             # gradient clipping: per group only the sum of squares; the coefficient and every update wait for the last group's partials
             clip = hasattr(self.opt, "clip_settings") and self.opt.clip_settings() is not None
+            # LAMB trust ratio: the three launches run over whole launch classes, so every update waits for the last group as well
+            lamb = hasattr(self.opt, "lamb_setting") and self.opt.lamb_setting()
             slot = 0
             for k, g in enumerate(self.graphs):
                 g.replay()
@@ -814,7 +820,7 @@ class GraphedTrainStep:
                         dist.all_reduce(xbuf[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
                     if clip:
                         slot = self.opt.sumsq_tables(tables[k], slot)
-                    else:
+                    elif not lamb:
                         self.opt.launch_tables(tables[k])
                     continue
                 self._events[k].record(cur)
@@ -832,13 +838,17 @@ class GraphedTrainStep:
                 with torch.cuda.stream(self._comm_stream):
                     if clip:
                         slot = self.opt.sumsq_tables(tables[k], slot)
-                    else:
+                    elif not lamb:
                         self.opt.launch_tables(tables[k])
-            if clip:
+            if clip or lamb:
                 with torch.cuda.stream(self._comm_stream) if overlap else contextlib.nullcontext():
-                    self.opt.clip_coef(slot)
-                    for t in tables:
-                        self.opt.launch_tables(t)
+                    if clip:
+                        self.opt.clip_coef(slot)
+                    if lamb:
+                        self.opt.launch_classes()
+                    else:
+                        for t in tables:
+                            self.opt.launch_tables(t)
             if overlap:
                 cur.wait_stream(self._comm_stream)
             self.opt.finish_group_step()

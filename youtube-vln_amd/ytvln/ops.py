@@ -1793,3 +1793,49 @@ def adamw_step_clip(p: Tensor, g: Tensor, m: Tensor, v: Tensor, chunks: Tensor, 
     _check(g, "g", g.dtype)
     call("ytvln_adamw_clip", _ptr(p), g.data_ptr(), dt, _ptr(m), _ptr(v), None if p_bf16 is None else p_bf16.data_ptr(),
          chunks.data_ptr(), int(nchunks), _ptr(hyper), float(grad_scale), _ptr(clip), _stream())
+
+
+def _check_i32(t: Tensor, name: str, n: int):
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+        raise RuntimeError(f"{name} must be a contiguous int32 GPU tensor of at least {n} entries")
+
+
+def lamb_stage1(p: Tensor, g: Tensor, m: Tensor, v: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor, partials: Tensor,
+                grad_scale: float = 1.0, clip: Optional[Tensor] = None):
+    """First pass of the LAMB update (include/ytvln.h: ytvln_lamb_stage1) over an AdamW chunk table, on the current stream: the moments, and
+    partials[2i], partials[2i+1] = sum p^2, sum r^2 of record i.  `g`: the fp32 gradient arena or the bf16 exchange buffer; `clip`: the
+    record of grad_clip_coef or None."""
+    for t, nme in ((p, "p"), (m, "m"), (v, "v"), (hyper, "hyper"), (partials, "partials")) + (((clip, "clip"),) if clip is not None else ()):
+        _check(t, nme)
+    dt = _grad_dtype(g)
+    _check(g, "g", g.dtype)
+    if partials.numel() < 2 * int(nchunks):
+        raise RuntimeError(f"lamb_stage1: {int(nchunks)} records, room for {partials.numel() // 2} pairs of partials")
+    call("ytvln_lamb_stage1", _ptr(p), g.data_ptr(), dt, _ptr(m), _ptr(v), chunks.data_ptr(), int(nchunks), _ptr(hyper), float(grad_scale),
+         _ptr(clip), _ptr(partials), _stream())
+
+
+def lamb_trust(partials: Tensor, chunks: Tensor, nchunks: int, tensor_first: Tensor, rec_tensor: Tensor, ntensors: int, trust: Tensor,
+               report: Tensor, clip: Optional[Tensor] = None):
+    """trust[k] and report[k] = [||p||, ||r||, trust, 0] for every tensor of a chunk table from the partials of lamb_stage1
+    (include/ytvln.h: ytvln_lamb_trust), on the current stream.  `tensor_first` (ntensors + 1 entries) and `rec_tensor` (one per record)
+    are the int32 tables of ytvln.optimization.lamb_tables; trust and report are indexed by rec_tensor's values."""
+    for t, nme in ((partials, "partials"), (trust, "trust"), (report, "report")) + (((clip, "clip"),) if clip is not None else ()):
+        _check(t, nme)
+    _check_i32(tensor_first, "tensor_first", int(ntensors) + 1)
+    _check_i32(rec_tensor, "rec_tensor", int(nchunks))
+    if partials.numel() < 2 * int(nchunks) or report.numel() != 4 * trust.numel():
+        raise RuntimeError("lamb_trust: partials must hold two values per record and report four per entry of trust")
+    call("ytvln_lamb_trust", _ptr(partials), chunks.data_ptr(), tensor_first.data_ptr(), rec_tensor.data_ptr(), int(ntensors), _ptr(trust),
+         _ptr(report), _ptr(clip), _stream())
+
+
+def lamb_stage2(p: Tensor, m: Tensor, v: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor, trust: Tensor, rec_tensor: Tensor,
+                clip: Optional[Tensor] = None, p_bf16: Optional[Tensor] = None):
+    """Second pass of the LAMB update (include/ytvln.h: ytvln_lamb_stage2): p -= lr * trust[rec_tensor[i]] * r over the chunk table, on the
+    current stream; `p_bf16` as in adamw_step."""
+    for t, nme in ((p, "p"), (m, "m"), (v, "v"), (hyper, "hyper"), (trust, "trust")) + (((clip, "clip"),) if clip is not None else ()):
+        _check(t, nme)
+    _check_i32(rec_tensor, "rec_tensor", int(nchunks))
+    call("ytvln_lamb_stage2", _ptr(p), _ptr(m), _ptr(v), None if p_bf16 is None else p_bf16.data_ptr(), chunks.data_ptr(), int(nchunks),
+         _ptr(hyper), _ptr(trust), rec_tensor.data_ptr(), _ptr(clip), _stream())

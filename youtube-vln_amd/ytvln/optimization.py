@@ -9,7 +9,8 @@ arenas, and a whole step is one HIP kernel launch per (param-group, step-count) 
 tensor x 541 tensors.  The flat gradient arena is also what the data-parallel all-reduce buckets (ytvln/distributed.py).
 
 Beyond the reference (it has no gradient clipping): two plain attributes, `optimizer.max_grad_norm` and `optimizer.skip_nonfinite`, bound
-the global gradient norm inside the step -- see the `AdamW` docstring.
+the global gradient norm inside the step, and `optimizer.trust_ratio` switches the update to LAMB's layer-wise trust ratio -- see the
+`AdamW` docstring.
 """
 from __future__ import annotations
 
@@ -27,6 +28,19 @@ from . import ops
 
 CHUNK = 16384       # elements per workgroup of the fused kernel
 ALIGN = 4           # arena offsets are multiples of 4 floats (16-byte vector access)
+
+
+def lamb_tables(tensors, chunk=CHUNK):
+    """The two int32 tables of the LAMB launches for one chunk table built from `tensors` = [(index in the arena, numel)] in table order
+    (every tensor cut into records of `chunk` elements, contiguous): (tensor_first: the first record of each tensor, len(tensors) + 1
+    entries; rec_tensor: the arena index of every record's tensor)."""
+    first, rec = [0], []
+    for k, numel in tensors:
+        if numel <= 0 or k < 0:
+            raise ValueError(f"lamb_tables: tensor {k} with {numel} elements")
+        rec += [int(k)] * ((numel + chunk - 1) // chunk)
+        first.append(len(rec))
+    return first, rec
 
 
 class ConstantLRSchedule(LambdaLR):
@@ -116,7 +130,19 @@ class AdamW(Optimizer):
 
     A captured step bakes both settings into the graph: changing either afterwards makes the next `prepare_replay()` raise; capture the
     step again.  Capturing with the feature on needs its two small device buffers, which the first eager step with the feature on (or
-    `clip_buffers()`) allocates."""
+    `clip_buffers()`) allocates.
+
+    trust_ratio (attribute, default False): True turns the update into LAMB (You et al., 2020) -- the AdamW direction with the decay inside
+        it, r = b * m / (sqrt(v) + eps) + wd * p (b: the bias correction), rescaled per parameter tensor: p -= lr * trust * r with
+        trust = ||p|| / ||r|| over the whole tensor.  Tensors of a group without weight decay (bias, LayerNorm: the BERT LAMB recipe) and
+        tensors with a zero or non-finite norm keep trust = 1.  The gradient is the one plain AdamW would read (after the exchange, times
+        grad_scale, times the clip coefficient with clipping on: LAMB's usual pre-normalisation IS max_grad_norm = 1).  Per launch class
+        three launches replace the one update: ytvln_lamb_stage1 (moments and per-record partial norms), ytvln_lamb_trust, ytvln_lamb_stage2
+        (the update, and the bf16 weight copy): 40 bytes per parameter against 28; no host synchronisation, no atomics, fixed summation
+        orders.  A plain attribute like the two above (anything but a bool raises ValueError when the step is taken), not in state_dict();
+        with False the decay stays after the update and a step launches exactly what it always launched.  Baked into a captured step like
+        the clip settings; its small buffers come from the first eager step with it on or from `lamb_buffers()`.  `trust_ratios()` is a
+        device view [tensors in arena order, 4] of the last step's rows [||p||, ||r||, trust, 0]."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
         if lr < 0.0:
@@ -137,6 +163,8 @@ class AdamW(Optimizer):
         self.max_grad_norm = None   # global gradient-norm clipping (class docstring); plain attributes, never part of state_dict()
         self.skip_nonfinite = False
         self._captured_clip = False  # the clipping settings recorded into the last captured step (False: nothing captured yet)
+        self.trust_ratio = False    # LAMB layer-wise trust ratio (class docstring); a plain attribute, never part of state_dict()
+        self._captured_lamb = None  # trust_ratio as recorded into the last captured step (None: nothing captured yet)
 
     # ---- arena management -----------------------------------------------------------------------------------------
     def _members(self):
@@ -177,7 +205,8 @@ class AdamW(Optimizer):
                 p.grad = flat["g"][o:o + n].view(p.shape)
                 st["exp_avg"] = flat["m"][o:o + n].view(p.shape)
                 st["exp_avg_sq"] = flat["v"][o:o + n].view(p.shape)
-        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None, partials=None, clip=None)
+        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None, partials=None, clip=None,
+                           lamb=None)
         self._launch = None
         del old
         # let the weight-gradient GEMMs write straight into the gradient arena and the packed projections alias the
@@ -310,9 +339,58 @@ class AdamW(Optimizer):
             return 0
         return int(a["clip"][3].item())
 
-    def _update(self, table, n, hyper):
+    # ---- LAMB layer-wise trust ratio ----------------------------------------------------------------------------------
+    def lamb_setting(self) -> bool:
+        """trust_ratio, validated: anything but a bool raises ValueError."""
+        if not isinstance(self.trust_ratio, bool):
+            raise ValueError(f"trust_ratio must be True or False, got {self.trust_ratio!r}")
+        return self.trust_ratio
+
+    def lamb_buffers(self):
+        """(partials, trust, report): two fp32 partials per CHUNK record of the arena, one trust ratio and one report row
+        [||p||, ||r||, trust, 0] per arena tensor.  Allocated on first use -- only with trust_ratio on -- and dropped with the arena; not
+        part of state_dict.  None before the arena exists."""
         a = self._arena
-        if self.clip_settings() is not None:
+        if a is None:
+            return None
+        if a["lamb"] is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("trust_ratio was switched on after the last eager step: take one eager step with it on (or call "
+                                   "lamb_buffers()) before capturing, so that its buffers do not live in a graph's pool")
+            dev, nt = a["g"].device, len(a["index"])
+            n = sum((numel + CHUNK - 1) // CHUNK for _, numel in a["index"].values())
+            a["lamb"] = (torch.zeros(2 * n, dtype=torch.float32, device=dev), torch.ones(nt, dtype=torch.float32, device=dev),
+                         torch.zeros(nt, 4, dtype=torch.float32, device=dev))
+            a["lamb_stepped"] = False
+        return a["lamb"]
+
+    def trust_ratios(self):
+        """Device tensor [tensors in arena order (arena_layout()), 4]: the rows [||p||, ||r||, trust, 0] of the last LAMB step, the norms
+        being those of the pre-update parameter and of the direction r.  A view -- no synchronisation; later steps overwrite it."""
+        a = self._arena
+        if a is None or a["lamb"] is None or not a["lamb_stepped"]:
+            raise RuntimeError("trust_ratios(): no step has been taken with trust_ratio = True")
+        return a["lamb"][2]
+
+    def _lamb_update(self, c):
+        """The three LAMB launches of launch class `c` on the current stream."""
+        a = self._arena
+        partials, trust, report = self.lamb_buffers()
+        clip = self.clip_buffers()[1] if self.clip_settings() is not None else None
+        part = partials[2 * c["rec0"]:2 * (c["rec0"] + c["n"])]
+        ops.lamb_stage1(a["p"], self._grad_operand(), a["m"], a["v"], c["table"], c["n"], c["hyper"], part, self.grad_scale, clip)
+        ops.lamb_trust(part, c["table"], c["n"], c["tensor_first"], c["rec_tensor"], c["ntensors"], trust, report, clip)
+        ops.lamb_stage2(a["p"], a["m"], a["v"], c["table"], c["n"], c["hyper"], trust, c["rec_tensor"], clip, p_bf16=a["pb"])
+        a["lamb_stepped"] = True
+
+    def _update(self, table, n, hyper, cls=None):
+        a = self._arena
+        if self.lamb_setting():
+            if cls is None or table is not cls["table"]:
+                raise RuntimeError("trust_ratio: the norms run over whole tensors, so the update runs over whole launch classes "
+                                   "(launch_classes()), not over pieces of their chunk tables")
+            self._lamb_update(cls)
+        elif self.clip_settings() is not None:
             ops.adamw_step_clip(a["p"], self._grad_operand(), a["m"], a["v"], table, n, hyper, self.clip_buffers()[1], self.grad_scale,
                                 p_bf16=a["pb"])
         elif self.exchange_dtype == torch.bfloat16:
@@ -350,7 +428,9 @@ class AdamW(Optimizer):
         for gi, p in members:
             classes.setdefault((gi, self.state[p]["step"]), []).append(p)
         index, dev = self._arena["index"], self._arena["p"].device
+        order = {pid: k for k, pid in enumerate(index)}          # a tensor's row in the trust / report buffers: its place in the arena
         launch = []
+        rec0 = 0
         for (gi, step), plist in classes.items():
             wd = float(self.param_groups[gi]["weight_decay"])
             rec = bytearray()
@@ -361,12 +441,17 @@ class AdamW(Optimizer):
                     rec += struct.pack("<qqff", o + c, min(CHUNK, numel - c), wd, 0.0)
                     n += 1
             table = torch.frombuffer(rec, dtype=torch.uint8).to(dev)
+            first, rec_tensor = lamb_tables([(order[id(p)], index[id(p)][1]) for p in plist])
+            assert len(rec_tensor) == n
             # hyper-parameters travel through a small ring of pinned host buffers (async H2D, no per-step stream sync);
             # an event per slot guards reuse should the host ever run a full ring ahead of the device.
-            launch.append(dict(group=gi, step=step, params=plist, table=table, n=n,
+            launch.append(dict(group=gi, step=step, params=plist, table=table, n=n, rec0=rec0, ntensors=len(plist),
+                               tensor_first=torch.tensor(first, dtype=torch.int32).to(dev),
+                               rec_tensor=torch.tensor(rec_tensor, dtype=torch.int32).to(dev),
                                hyper=torch.zeros(8, dtype=torch.float32, device=dev),
                                ring=[torch.zeros(8, dtype=torch.float32).pin_memory() for _ in range(4)],
                                events=[None] * 4, slot=0))
+            rec0 += n
         self._launch = launch
 
     def load_state_dict(self, state_dict):
@@ -382,20 +467,22 @@ class AdamW(Optimizer):
 
     # ---- the step -------------------------------------------------------------------------------------------------
     def _upload_hyper(self):
-        """Host -> device upload of (beta1, beta2, eps, step_size, lr) for every launch class and advance of the step
+        """Host -> device upload of (beta1, beta2, eps, step_size, lr, bias correction) for every launch class and advance of the step
         counters.  Eager by design: under hipGraph replay (`capturing=True` steps) this is the only per-step host work."""
         for c in self._launch:
             g = self.param_groups[c["group"]]
             b1, b2 = g["betas"]
             t = c["step"] + 1
-            step_size = g["lr"]
+            step_size, bias = g["lr"], 1.0
             if g["correct_bias"]:
                 step_size = step_size * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+                bias = math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
             k = c["slot"] = (c["slot"] + 1) % 4
             if c["events"][k] is not None:
                 c["events"][k].synchronize()
             host = c["ring"][k]
             host[0], host[1], host[2], host[3], host[4] = b1, b2, g["eps"], step_size, g["lr"]
+            host[5] = bias              # read by the LAMB launches only (trust_ratio)
             c["hyper"].copy_(host, non_blocking=True)
             c["events"][k] = torch.cuda.Event()
             c["events"][k].record()
@@ -408,8 +495,8 @@ class AdamW(Optimizer):
             self.clip_coef(self.sumsq_tables([(ci, c["table"], c["n"]) for ci, c in enumerate(self._launch)], 0))
         if torch.cuda.is_current_stream_capturing():
             self._captured_clip = self.clip_settings()
-        for c in self._launch:
-            self._update(c["table"], c["n"], c["hyper"])
+            self._captured_lamb = self.lamb_setting()
+        self.launch_classes()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -418,6 +505,7 @@ class AdamW(Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self.clip_settings()              # invalid max_grad_norm: ValueError before anything is exchanged, launched or recorded
+        self.lamb_setting()               # (and an invalid trust_ratio)
         if torch.cuda.is_current_stream_capturing():
             # inside a hipGraph capture of a whole training step: only the device work is recorded; the caller uploads the
             # hyper-parameters eagerly before every replay (`prepare_replay()`).  The arena must already exist.
@@ -513,6 +601,11 @@ class AdamW(Optimizer):
             owner._group_tables_cache = (self._launch, out)
         return out
 
+    def launch_classes(self):
+        """The update of every launch class over its whole chunk table, on the current stream: the form the LAMB update (trust_ratio) needs."""
+        for c in self._launch:
+            self._update(c["table"], c["n"], c["hyper"], c)
+
     def launch_tables(self, tables):
         """The fused AdamW kernels of one group, on the current stream (hyper-parameters come from prepare_replay())."""
         for ci, table, n in tables:
@@ -539,10 +632,13 @@ class AdamW(Optimizer):
 
     def prepare_replay(self):
         """Call before each replay of a captured training step (after scheduler.step() set the new learning rate).  The captured step
-        carries the clipping settings it was recorded with: raises if max_grad_norm / skip_nonfinite changed since."""
+        carries the clipping settings and trust_ratio it was recorded with: raises if one of them changed since."""
         if self._captured_clip is not False and self.clip_settings() != self._captured_clip:
             raise RuntimeError(f"max_grad_norm / skip_nonfinite changed since the step was captured (captured {self._captured_clip}, now "
                                f"{self.clip_settings()}): the graph holds the old launches -- capture the step again")
+        if self._captured_lamb is not None and self.lamb_setting() != self._captured_lamb:
+            raise RuntimeError(f"trust_ratio changed since the step was captured (captured {self._captured_lamb}, now {self.trust_ratio}): "
+                               "the graph holds the old launches -- capture the step again")
         self._upload_hyper()
 
     def zero_grad(self, set_to_none: bool = True):

@@ -65,6 +65,8 @@ def get_optimization(args, model, train_data_loader_length, logger):
     # global gradient-norm clipping (beyond the reference; ytvln.optimization.AdamW): argument objects without the fields leave it off
     optimizer.max_grad_norm = getattr(args, "max_grad_norm", None)
     optimizer.skip_nonfinite = bool(getattr(args, "skip_nonfinite_grads", False))
+    if hasattr(args, "lamb"):                 # LAMB layer-wise trust ratio (beyond the reference as well); validated when a step is taken
+        optimizer.trust_ratio = args.lamb
     scheduler = build_scheduler(args, optimizer, train_data_loader_length)
     start_epoch = 0
     if getattr(args, "resume", False):
