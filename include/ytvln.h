@@ -318,8 +318,8 @@ int ytvln_attn_bwd_bf16(const ytvln_attn_problem* a, const ytvln_attn_problem* b
  * (n < N, h < heads, i < Tq, j < Tk) addressed through the strides lies inside the allocation -- the library cannot check an extent.
  * Checked: stride_q and stride_k are non-negative and (Tq-1) stride_q + (Tk-1) stride_k < 2^31 (offsets inside a (pair, head) plane are
  * 32-bit); stride_n and stride_h are 64-bit, may have either sign, and fall under the caller's contract alone.  Values
- * are finite or -inf; a query row whose scores are ALL -inf is NaN in the reference and unspecified here.  The bias is a constant: no
- * gradient with respect to it is computed.  A NULL record or a NULL `ptr` means "no bias", so one call serves a pair with one biased side;
+ * are finite or -inf; a query row whose scores are ALL -inf is NaN in the reference and unspecified here.  The forward / backward entry
+ * points below treat the bias as a constant; its gradient is a launch of its own, ytvln_attn_dbias_* further down (unfused by design).  A NULL record or a NULL `ptr` means "no bias", so one call serves a pair with one biased side;
  * a launch in which no problem has a bias runs exactly the kernels of the entry points above.  Problems WITH a bias run the two-wave / wave-pair
  * fp32 kernels (never the one-wave forms selected by ATTN_W1) -- decided per launch.  softmax, lse, dropout decisions: unchanged. */
 typedef struct ytvln_attn_bias {
@@ -343,6 +343,34 @@ int ytvln_attn_bwd_bias_bf16(const ytvln_attn_problem* a, const ytvln_attn_bias*
  * returns are the biased ones); `bias` NULL or bias->ptr NULL = ytvln_attn_probs_f32. */
 int ytvln_attn_probs_bias_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* mask, const ytvln_attn_bias* bias,
                               const float* lse, float* probs, int N, int heads, int Tq, int Tk, int d, float scale, void* stream);
+
+/* Gradient with respect to the per-score bias (what autograd gives a float attn_mask of torch attention; the reference never trains one).  The
+ * bias is added to the final score, so dBias = dS.  UNFUSED by design: a launch of its own recomputes, per 32x32 block of scores on the fp32
+ * matrix cores (v_mfma_f32_32x32x2_f32; bf16 operands are widened exactly), two of the backward's five products,
+ *     s  = fadd(fadd(fmul(q_i.k_j, scale), mask[n,j]), bias[n,h,i,j])      the forward's score, same roundings
+ *     p  = exp(s - lse[n,h,i])          dp = dO_i.v_j          dS[n,h,i,j] = p * (keep/(1 - p_drop) * dp - delta[n,h,i])
+ * and stores one score-sized fp32 tensor; the forward / backward kernels and every existing launch are untouched.  `p` is the problem record
+ * of the BACKWARD launch of the same problem and the call is enqueued AFTER that launch on the same stream: it reads q, k, v, mask, dctx,
+ * lse_in and the delta = sum_c dO.O that launch wrote (plus Tq, Tk, p_drop, site, the leading dimensions).  Dropout decisions are the
+ * forward's: _f32 re-draws the hash from (rng, site, element) exactly as ytvln_attn_fwd_f32 does, _bf16 reads the keep bits ytvln_attn_fwd_bf16
+ * stored (p->keep).  `bias`: the record of the FORWARD values (NULL or NULL ptr: none was added).  A score with p == 0 (masked key, -inf bias)
+ * gets exactly 0.
+ *   `out` is described like the bias -- fp32 pointer (WRITTEN, every addressed element) plus element strides over [N or 1, heads or 1, Tq, Tk];
+ * checked like a bias (4-byte alignment, non-negative stride_q / stride_k, plane span < 2^31); the addressed elements must not overlap.
+ * stride_n == 0 means extent 1 over pairs and stride_h == 0 extent 1 over heads: such a dimension is SUMMED OVER inside the library, in fp32,
+ * without atomics and in a fixed order (bit-reproducible): the reduced (pair, head) problems are numbered r = n * heads + h (pair-major) over
+ * the reduced dimensions only, cut into ytvln_attn_dbias_chunks(...) runs of equal length (the last one shorter); one wave adds the blocks of a
+ * run in ascending r; with more than one run each writes a partial plane to `workspace` and a second launch adds the runs in ascending order.
+ *   workspace: ytvln_attn_dbias_workspace_elems(out, N, heads, Tq, Tk) floats = runs x the dense size of the output when runs > 1, else 0 (may
+ * be NULL then).  The number of runs depends on the shapes alone, never on the device: 1 when at most 16 problems are summed per output plane
+ * ([N,heads,..] always, [N,1,..] up to 16 heads); otherwise as many as bring the launch to 1024 waves, but at least 4 problems per run.
+ *   d: _f32 any multiple of 4 up to 128, _bf16 64 or 128 (q, k, v, dctx are bf16 there; mask, lse, delta, bias, out stay fp32). */
+int ytvln_attn_dbias_chunks(const ytvln_attn_bias* out, int N, int heads, int Tq, int Tk);
+int64_t ytvln_attn_dbias_workspace_elems(const ytvln_attn_bias* out, int N, int heads, int Tq, int Tk);
+int ytvln_attn_dbias_f32(const ytvln_attn_problem* p, const ytvln_attn_bias* bias, const ytvln_attn_bias* out, float* workspace,
+                         int64_t workspace_elems, int N, int heads, int d, float scale, const int64_t* rng, void* stream);
+int ytvln_attn_dbias_bf16(const ytvln_attn_problem* p, const ytvln_attn_bias* bias, const ytvln_attn_bias* out, float* workspace,
+                          int64_t workspace_elems, int N, int heads, int d, float scale, const int64_t* rng, void* stream);
 
 /* probs[n,h,i,j] = exp(q_i.k_j*scale + mask - lse): the attention_probs tensor the reference returns when
  * output_all_attention_masks=True (vilbert.py:300, 311).  Diagnostic path, not on the training step. */

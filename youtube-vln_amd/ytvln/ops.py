@@ -1468,10 +1468,43 @@ def _attn_bwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, dout, lse,
         _attn_launch(True, bf16, _attn_problem(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, Tq, Tk, p, site, ctx_in=out, dctx=dout,
                                                lse_in=lse, delta=delta, dq=dq, dq_off=dq_off, lddq=lddq, dk=dk, dk_off=dk_off, lddk=lddk,
                                                dv=dv, dv_off=dv_off, lddv=lddv, keep=keep), None, N, heads, d, scale, rng, ba=brec)
-        return
+        return delta
     call("ytvln_attn_bwd_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(v, v_off), ldv, _ptr(mask), _ptr(out), _ptr(dout),
          out.shape[-1], _ptr(lse), _ptr(delta), _ptr(dq, dq_off), lddq, _ptr(dk, dk_off), lddk, _ptr(dv, dv_off), lddv, N, heads, Tq,
          Tk, d, float(scale), float(p), _ptr(rng) if rng is not None else None, int(site), _stream())
+    return delta
+
+
+def _trainable_bias(bias: Optional[Tensor], needs_grad: bool):
+    """-> (the tensor the launches read, (shape, dtype) of the gradient to return or None).  A bias that autograd wants a gradient for reaches the
+    launches as a detached fp32 view (`_attn_bias` refuses one that requires grad: a raw launch computes no bias gradient); every other bias
+    passes through untouched."""
+    if bias is None or not needs_grad:
+        return bias, None
+    b = bias.detach()
+    return (b if b.dtype == torch.float32 else b.float()), (tuple(bias.shape), bias.dtype)
+
+
+def _attn_dbias(pr, bias: Optional[Tensor], like, bf16: bool, N, heads, Tq, Tk, d, scale, rng, device) -> Tensor:
+    """Gradient of a trainable per-score bias (`ytvln_attn_dbias_*`, include/ytvln.h), enqueued behind the backward launch of the same problem:
+    `pr` is that launch's problem record (its delta buffer is read), `bias` the detached forward values, `like` = (shape, dtype) of the bias
+    argument.  The result is a fresh contiguous buffer of that shape: a dimension of size 1 is summed over inside the library; an expanded
+    one (stride 0, size > 1) gets its full gradient and autograd's expand-backward sums it; a transposed view gets the gradient of the view."""
+    shape, dtype = like
+    g = torch.empty(shape, dtype=torch.float32, device=device)
+    orec = _lib.AttnBias()
+    orec.ptr = g.data_ptr()
+    orec.stride_n, orec.stride_h, orec.stride_q, orec.stride_k = attn_bias_strides(g, N, heads, Tq, Tk)
+    brec = None
+    if bias is not None:
+        brec = _lib.AttnBias()
+        brec.ptr = bias.data_ptr()
+        brec.stride_n, brec.stride_h, brec.stride_q, brec.stride_k = attn_bias_strides(bias, N, heads, Tq, Tk)
+    need = int(_lib.load().ytvln_attn_dbias_workspace_elems(ctypes.addressof(orec), N, heads, Tq, Tk))
+    ws = torch.empty(need, dtype=torch.float32, device=device) if need > 0 else None
+    call("ytvln_attn_dbias_bf16" if bf16 else "ytvln_attn_dbias_f32", ctypes.addressof(pr), ctypes.addressof(brec) if brec is not None else None,
+         ctypes.addressof(orec), _ptr(ws), need, N, heads, d, float(scale), _ptr(rng) if rng is not None else None, _stream())
+    return g if dtype == torch.float32 else g.to(dtype)
 
 
 def attn_probs(q, q_off, ldq, k, k_off, ldk, mask, lse, N, heads, Tq, Tk, d, scale, bias=None) -> Tensor:
@@ -1498,7 +1531,7 @@ class SelfAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, mask, N, T, heads, p, rng, site, *opt):
-        bias = opt[0] if opt else None
+        bias, ctx.bias_like = _trainable_bias(opt[0] if opt else None, bool(opt) and ctx.needs_input_grad[8])
         ctx.n_in = 8 + len(opt)
         ctx.set_materialize_grads(False)
         _check(qkv, "qkv", qkv.dtype if qkv.dtype == torch.bfloat16 else torch.float32)
@@ -1526,9 +1559,15 @@ class SelfAttentionFn(torch.autograd.Function):
         if dout.dtype != qkv.dtype:
             dout = dout.to(qkv.dtype)
         dqkv = torch.empty_like(qkv)
-        _attn_bwd(qkv, 0, 3 * H, qkv, H, 3 * H, qkv, 2 * H, 3 * H, mask, out, dout, lse, dqkv, 0, 3 * H, dqkv, H, 3 * H, dqkv, 2 * H,
-                  3 * H, N, heads, T, T, d, scale, p, rng, site, keep=keep, bias=bias)
-        return (dqkv,) + (None,) * (ctx.n_in - 1)
+        delta = _attn_bwd(qkv, 0, 3 * H, qkv, H, 3 * H, qkv, 2 * H, 3 * H, mask, out, dout, lse, dqkv, 0, 3 * H, dqkv, H, 3 * H, dqkv, 2 * H,
+                          3 * H, N, heads, T, T, d, scale, p, rng, site, keep=keep, bias=bias)
+        if ctx.bias_like is None:
+            return (dqkv,) + (None,) * (ctx.n_in - 1)
+        # trainable bias: dBias = dS, recomputed by a launch of its own behind the backward (unfused by design, include/ytvln.h)
+        pr = _attn_problem(qkv, 0, 3 * H, qkv, H, 3 * H, qkv, 2 * H, 3 * H, mask, T, T, p, site, ctx_in=out, dctx=dout, lse_in=lse, delta=delta,
+                           keep=keep)
+        gb = _attn_dbias(pr, bias, ctx.bias_like, qkv.dtype == torch.bfloat16, N, heads, T, T, d, scale, rng, qkv.device)
+        return (dqkv,) + (None,) * 7 + (gb,)
 
 
 class CoAttentionFn(torch.autograd.Function):
@@ -1544,6 +1583,8 @@ class CoAttentionFn(torch.autograd.Function):
         """opt: (bias1, bias2) -- per-score biases of the two directions, [.., T, R] for ctx1 and [.., R, T] for ctx2 (either may be None)."""
         bias1, bias2 = (tuple(opt) + (None, None))[:2]
         ctx.n_in = 15 + len(opt)
+        bias1, ctx.bias1_like = _trainable_bias(bias1, len(opt) > 0 and ctx.needs_input_grad[15])
+        bias2, ctx.bias2_like = _trainable_bias(bias2, len(opt) > 1 and ctx.needs_input_grad[16])
         bias1, b1 = _attn_bias(bias1, N, heads, T, R)
         bias2, b2 = _attn_bias(bias2, N, heads, R, T)
         bf16 = q1.dtype == torch.bfloat16
@@ -1579,29 +1620,45 @@ class CoAttentionFn(torch.autograd.Function):
         N, R, T, heads, Hb, d, scale, p1, p2, site1, site2 = ctx.meta
         nn_ = (None,) * (ctx.n_in - 4)
         gq1 = gkv1 = gq2 = gkv2 = None
+        bf16 = q1.dtype == torch.bfloat16
+        want1, want2 = ctx.bias1_like is not None, ctx.bias2_like is not None          # trainable biases: each live direction's gets its own gradient
+
+        def tail(gb1, gb2):
+            return nn_ if not (want1 or want2) else (None,) * 11 + (gb1, gb2)[:ctx.n_in - 15]
         if d1 is not None and d2 is not None:       # the usual case: both directions in one launch per kernel
             d1 = d1 if d1.is_contiguous() else d1.contiguous()
             d2 = d2 if d2.is_contiguous() else d2.contiguous()
             gq2, gkv1, gq1, gkv2 = torch.empty_like(q2), torch.empty_like(kv1), torch.empty_like(q1), torch.empty_like(kv2)
             delta1, delta2 = torch.empty_like(lse1), torch.empty_like(lse2)
-            _attn_launch(True, q1.dtype == torch.bfloat16,
-                       _attn_problem(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, T, R, p1, site1, ctx_in=ctx1, dctx=d1, lse_in=lse1,
-                                     delta=delta1, dq=gq2, lddq=Hb, dk=gkv1, lddk=2 * Hb, dv=gkv1, dv_off=Hb, lddv=2 * Hb, keep=keep1),
-                       _attn_problem(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, R, T, p2, site2, ctx_in=ctx2, dctx=d2, lse_in=lse2,
-                                     delta=delta2, dq=gq1, lddq=Hb, dk=gkv2, lddk=2 * Hb, dv=gkv2, dv_off=Hb, lddv=2 * Hb, keep=keep2),
-                       N, heads, d, scale, rng, ba=_attn_bias(bias1, N, heads, T, R)[1], bb=_attn_bias(bias2, N, heads, R, T)[1])
-            return (gq1, gkv1, gq2, gkv2) + nn_
+            pa = _attn_problem(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, T, R, p1, site1, ctx_in=ctx1, dctx=d1, lse_in=lse1,
+                               delta=delta1, dq=gq2, lddq=Hb, dk=gkv1, lddk=2 * Hb, dv=gkv1, dv_off=Hb, lddv=2 * Hb, keep=keep1)
+            pb = _attn_problem(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, R, T, p2, site2, ctx_in=ctx2, dctx=d2, lse_in=lse2,
+                               delta=delta2, dq=gq1, lddq=Hb, dk=gkv2, lddk=2 * Hb, dv=gkv2, dv_off=Hb, lddv=2 * Hb, keep=keep2)
+            _attn_launch(True, bf16, pa, pb, N, heads, d, scale, rng, ba=_attn_bias(bias1, N, heads, T, R)[1],
+                         bb=_attn_bias(bias2, N, heads, R, T)[1])
+            gb1 = _attn_dbias(pa, bias1, ctx.bias1_like, bf16, N, heads, T, R, d, scale, rng, q1.device) if want1 else None
+            gb2 = _attn_dbias(pb, bias2, ctx.bias2_like, bf16, N, heads, R, T, d, scale, rng, q1.device) if want2 else None
+            return (gq1, gkv1, gq2, gkv2) + tail(gb1, gb2)
+        gb1 = gb2 = None          # (a direction whose context gradient is None returns None for its bias)
         if d1 is not None:      # text queries over image keys/values -> dq2, dk1|dv1
             d1 = d1 if d1.is_contiguous() else d1.contiguous()
             gq2, gkv1 = torch.empty_like(q2), torch.empty_like(kv1)
-            _attn_bwd(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, ctx1, d1, lse1, gq2, 0, Hb, gkv1, 0, 2 * Hb, gkv1, Hb,
-                      2 * Hb, N, heads, T, R, d, scale, p1, rng, site1, keep=keep1, bias=bias1)
+            delta1 = _attn_bwd(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, ctx1, d1, lse1, gq2, 0, Hb, gkv1, 0, 2 * Hb, gkv1, Hb,
+                               2 * Hb, N, heads, T, R, d, scale, p1, rng, site1, keep=keep1, bias=bias1)
+            if want1:
+                pa = _attn_problem(q2, 0, Hb, kv1, 0, 2 * Hb, kv1, Hb, 2 * Hb, mask1, T, R, p1, site1, ctx_in=ctx1, dctx=d1, lse_in=lse1,
+                                   delta=delta1, keep=keep1)
+                gb1 = _attn_dbias(pa, bias1, ctx.bias1_like, bf16, N, heads, T, R, d, scale, rng, q1.device)
         if d2 is not None:      # image queries over text keys/values -> dq1, dk2|dv2
             d2 = d2 if d2.is_contiguous() else d2.contiguous()
             gq1, gkv2 = torch.empty_like(q1), torch.empty_like(kv2)
-            _attn_bwd(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, ctx2, d2, lse2, gq1, 0, Hb, gkv2, 0, 2 * Hb, gkv2, Hb,
-                      2 * Hb, N, heads, R, T, d, scale, p2, rng, site2, keep=keep2, bias=bias2)
-        return (gq1, gkv1, gq2, gkv2) + nn_
+            delta2 = _attn_bwd(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, ctx2, d2, lse2, gq1, 0, Hb, gkv2, 0, 2 * Hb, gkv2, Hb,
+                               2 * Hb, N, heads, R, T, d, scale, p2, rng, site2, keep=keep2, bias=bias2)
+            if want2:
+                pb = _attn_problem(q1, 0, Hb, kv2, 0, 2 * Hb, kv2, Hb, 2 * Hb, mask2, R, T, p2, site2, ctx_in=ctx2, dctx=d2, lse_in=lse2,
+                                   delta=delta2, keep=keep2)
+                gb2 = _attn_dbias(pb, bias2, ctx.bias2_like, bf16, N, heads, R, T, d, scale, rng, q1.device)
+        return (gq1, gkv1, gq2, gkv2) + tail(gb1, gb2)
 
 
 # ------------------------------------------------------------------------------------------------------------------
