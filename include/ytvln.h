@@ -469,6 +469,17 @@ int ytvln_lamb_trust(const float* partials, const void* chunks, const int32_t* t
  * p -= lr * trust[rec_tensor[i]] * r and writes p, and bf16(p) into p_bf16 when that is not NULL.  16 bytes per parameter, 18 with the copy. */
 int ytvln_lamb_stage2(float* p, const float* m, const float* v, uint16_t* p_bf16, const void* chunks, int nchunks, const float* hyper,
                       const float* trust, const int32_t* rec_tensor, const float* clip, void* stream);
+/* EMA of the weights (timm's ModelEmaV2; the reference has none): a shadow arena e with the offsets of the parameter arena, updated by a
+ * launch of its own behind the update launches of a chunk table:
+ *   e = fma(w, p - e, e)   in fp32, w = hyper[6] = float32(1 - decay), p: the parameter the update just wrote
+ * (the lerp form: p == e leaves e bit-unchanged for every w).  `clip` is the record of ytvln_grad_clip_coef or NULL; with clip[2] != 0 (a
+ * skipped step) the launch returns before writing anything.  One workgroup per record; elements outside the table are not touched; p is
+ * read-only.  Both arenas 16-byte aligned.  12 bytes per parameter. */
+int ytvln_ema_update(const float* p, float* e, const void* chunks, int nchunks, const float* hyper, const float* clip, void* stream);
+/* Exchanges p[i] and e[i] for every element of the table (evaluation with the shadow weights; two calls are the identity) and, when p_bf16
+ * is not NULL, writes p_bf16[i] = bf16(new p[i]) (round to nearest even) at the same offsets.  All arenas 16-byte aligned.  16 bytes per
+ * parameter, 18 with the copy. */
+int ytvln_ema_swap(float* p, float* e, uint16_t* p_bf16, const void* chunks, int nchunks, void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI ------------------------------------------------------------------------
  * Replaces DistributedDataParallel over NCCL (utils/distributed.py:63-104: init_process_group("nccl") + DDP's bucketed all-reduce).

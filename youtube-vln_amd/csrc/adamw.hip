@@ -10,6 +10,9 @@
 // (grad_clip_coef_kernel) and an instantiation of the update that reads its gradient scale from the four-float record that reduction wrote.
 // Opt-in LAMB layer-wise trust ratio splits the update into two streaming passes around a per-tensor reduction (lamb_stage1_kernel: 24 bytes
 // per parameter, lamb_trust_kernel, lamb_stage2_kernel: 16, 18 with the bf16 copy): 40 bytes per parameter against 28.
+// Opt-in EMA of the weights keeps a shadow arena with the offsets of the parameter arena: ema_update_kernel is a launch of its own behind the
+// update (12 bytes per parameter; fused into the update it would be 8, at the price of a sixth instantiation of the audited kernels), and
+// ema_swap_kernel exchanges parameters and shadow for evaluation (16 bytes per parameter, 18 with the bf16 copy).
 #include "common.h"
 
 namespace ytvln {
@@ -286,6 +289,72 @@ __global__ __launch_bounds__(256) void lamb_stage2_kernel(float* __restrict__ P,
     }
 }
 
+// ---- EMA of the weights (timm's ModelEmaV2), opt-in: a shadow arena e with the offsets of the parameter arena ------------------------------
+//   e = fma(w, p - e, e)      w = hyper[6] = float32(1 - decay), p: the parameter the update launch before this one just wrote
+// The lerp form: p == e gives p - e = 0 and fma(w, 0, e) = e, so a parameter that equals its shadow leaves the shadow's bits alone for every w
+// (the one exception is the sign of a zero: p = e = -0 gives +0).  The product-sum is an explicit fma, so the float4 body and the scalar
+// tail round alike (the hazard adam1 / adam1_tail document).  One workgroup per chunk record, four 16-byte loads of each arena in flight per
+// thread as in grad_pack_bf16_kernel; no LDS, no atomics; elements outside the records are not touched.  `clip` (may be NULL) is the record
+// of grad_clip_coef_kernel: skip != 0 makes the launch return before writing anything, as the update it follows did.  Reads p, e; writes e:
+// 12 bytes per parameter.
+__device__ __forceinline__ float ema1(float p, float e, float w) { return __builtin_fmaf(w, p - e, e); }
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ P, float* __restrict__ E, const AdamChunk* __restrict__ chunks,
+                                                         const float* __restrict__ hyper, const float* __restrict__ clip) {
+    if (clip && clip[2] != 0.f) return;
+    const AdamChunk c = chunks[blockIdx.x];
+    const float w = hyper[6];
+    const float* p = P + c.off; float* e = E + c.off;
+    const int64_t n4 = ((c.off & 3) == 0) ? (c.len >> 2) : 0;
+    for (int64_t i = threadIdx.x; i < n4; i += 4 * 256) {
+        float4 x[4], y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool in = i + k * 256 < n4;
+            x[k] = in ? reinterpret_cast<const float4*>(p)[i + k * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
+            y[k] = in ? reinterpret_cast<const float4*>(e)[i + k * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + k * 256 < n4)
+                reinterpret_cast<float4*>(e)[i + k * 256] = make_float4(ema1(x[k].x, y[k].x, w), ema1(x[k].y, y[k].y, w),
+                                                                        ema1(x[k].z, y[k].z, w), ema1(x[k].w, y[k].w, w));
+    }
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) e[i] = ema1(p[i], e[i], w);
+}
+
+// Exchanges p and e element by element over a chunk table (evaluation with the shadow weights: contents move, every view of the arenas
+// stays valid); PB != nullptr: bf16(new p), round to nearest even, is written at the same offsets -- the weight operands of the bf16-resident
+// path follow the swap in the same pass.  16 bytes per parameter, 18 with the copy.
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ P, float* __restrict__ E, uint16_t* __restrict__ PB,
+                                                       const AdamChunk* __restrict__ chunks) {
+    const AdamChunk c = chunks[blockIdx.x];
+    float* p = P + c.off; float* e = E + c.off;
+    const int64_t n4 = ((c.off & 3) == 0) ? (c.len >> 2) : 0;
+    for (int64_t i = threadIdx.x; i < n4; i += 4 * 256) {
+        float4 x[4], y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool in = i + k * 256 < n4;
+            x[k] = in ? reinterpret_cast<const float4*>(p)[i + k * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
+            y[k] = in ? reinterpret_cast<const float4*>(e)[i + k * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + k * 256 < n4) {
+                reinterpret_cast<float4*>(p)[i + k * 256] = y[k];
+                reinterpret_cast<float4*>(e)[i + k * 256] = x[k];
+                if (PB) reinterpret_cast<uint2*>(PB + c.off)[i + k * 256] = make_uint2(bf16_bits(y[k].x) | (bf16_bits(y[k].y) << 16),
+                                                                                     bf16_bits(y[k].z) | (bf16_bits(y[k].w) << 16));
+            }
+    }
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) {
+        const float x = p[i], y = e[i];
+        p[i] = y; e[i] = x;
+        if (PB) PB[c.off + i] = (uint16_t)bf16_bits(y);
+    }
+}
+
 }  // namespace ytvln
 
 using namespace ytvln;
@@ -419,5 +488,26 @@ extern "C" int ytvln_lamb_stage2(float* p, const float* m, const float* v, uint1
     hipLaunchKernelGGL(lamb_stage2_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), p, m, v, p_bf16,
                        reinterpret_cast<const AdamChunk*>(chunks), hyper, trust, rec_tensor, clip);
     YT_LAUNCH_CHECK("lamb_stage2");
+    return 0;
+}
+
+extern "C" int ytvln_ema_update(const float* p, float* e, const void* chunks, int nchunks, const float* hyper, const float* clip, void* stream) {
+    YT_REQUIRE(p && e && chunks && hyper, "ema_update: null pointer");
+    YT_REQUIRE((((uintptr_t)p | (uintptr_t)e) & 15) == 0, "ema_update: arenas must be 16-byte aligned");
+    YT_REQUIRE(nchunks >= 0, "ema_update: nchunks = %d", nchunks);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), p, e, reinterpret_cast<const AdamChunk*>(chunks),
+                       hyper, clip);
+    YT_LAUNCH_CHECK("ema_update");
+    return 0;
+}
+
+extern "C" int ytvln_ema_swap(float* p, float* e, uint16_t* p_bf16, const void* chunks, int nchunks, void* stream) {
+    YT_REQUIRE(p && e && chunks, "ema_swap: null pointer");
+    YT_REQUIRE((((uintptr_t)p | (uintptr_t)e | (uintptr_t)p_bf16) & 15) == 0, "ema_swap: arenas must be 16-byte aligned");
+    YT_REQUIRE(nchunks >= 0, "ema_swap: nchunks = %d", nchunks);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), p, e, p_bf16, reinterpret_cast<const AdamChunk*>(chunks));
+    YT_LAUNCH_CHECK("ema_swap");
     return 0;
 }

@@ -94,6 +94,8 @@ SIGNATURES = {
     "ytvln_lamb_stage1": [P, P, I32, P, P, P, I32, P, F32, P, P, P],
     "ytvln_lamb_trust": [P, P, P, P, I32, P, P, P, P],
     "ytvln_lamb_stage2": [P, P, P, P, P, I32, P, P, P, P, P],
+    "ytvln_ema_update": [P, P, P, I32, P, P, P],
+    "ytvln_ema_swap": [P, P, P, P, I32, P],
     "ytvln_ln_fwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, I64, P],
     "ytvln_ln_bwd_blocks": [I64],
     "ytvln_ln_bwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],

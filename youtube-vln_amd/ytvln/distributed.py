@@ -598,6 +598,8 @@ class GraphedTrainStep:
             optimizer.clip_buffers()        # gradient clipping on: its partials and its record, eagerly as well
         if hasattr(optimizer, "lamb_setting") and optimizer.lamb_setting():
             optimizer.lamb_buffers()        # LAMB trust ratio on: its partials, ratios and report rows
+        if hasattr(optimizer, "ema_setting") and optimizer.ema_setting() is not None:
+            optimizer.ema_buffers()         # EMA of the weights on: its shadow arena
         torch.cuda.synchronize()
         flat = optimizer.flat_grad()
         # the buffer the collectives work on: the fp32 arena, or its bf16 copy (same offsets; slices stay element ranges)

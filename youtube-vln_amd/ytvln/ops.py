@@ -1896,3 +1896,25 @@ def lamb_stage2(p: Tensor, m: Tensor, v: Tensor, chunks: Tensor, nchunks: int, h
     _check_i32(rec_tensor, "rec_tensor", int(nchunks))
     call("ytvln_lamb_stage2", _ptr(p), _ptr(m), _ptr(v), None if p_bf16 is None else p_bf16.data_ptr(), chunks.data_ptr(), int(nchunks),
          _ptr(hyper), _ptr(trust), rec_tensor.data_ptr(), _ptr(clip), _stream())
+
+
+def ema_update(p: Tensor, e: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor, clip: Optional[Tensor] = None):
+    """e = fma(w, p - e, e) with w = hyper[6] over an AdamW chunk table (include/ytvln.h: ytvln_ema_update), on the current stream: the EMA
+    of the weights behind an update launch.  `clip`: the record of grad_clip_coef or None; a skipped step leaves `e` untouched."""
+    for t, nme in ((p, "p"), (e, "e"), (hyper, "hyper")) + (((clip, "clip"),) if clip is not None else ()):
+        _check(t, nme)
+    if e.numel() != p.numel() or hyper.numel() < 8:
+        raise RuntimeError("ema_update: the shadow arena must have the size of the parameter arena and hyper eight floats")
+    call("ytvln_ema_update", _ptr(p), _ptr(e), chunks.data_ptr(), int(nchunks), _ptr(hyper), _ptr(clip), _stream())
+
+
+def ema_swap(p: Tensor, e: Tensor, chunks: Tensor, nchunks: int, p_bf16: Optional[Tensor] = None):
+    """Exchange p and e over an AdamW chunk table (include/ytvln.h: ytvln_ema_swap), on the current stream; `p_bf16` as in adamw_step: the
+    bf16 copy of the new p is written by the same pass."""
+    _check(p, "p")
+    _check(e, "e")
+    if p_bf16 is not None:
+        _check(p_bf16, "p_bf16", torch.bfloat16)
+    if e.numel() != p.numel() or (p_bf16 is not None and p_bf16.numel() != p.numel()):
+        raise RuntimeError("ema_swap: the shadow arena and the bf16 copy must have the size of the parameter arena")
+    call("ytvln_ema_swap", _ptr(p), _ptr(e), None if p_bf16 is None else p_bf16.data_ptr(), chunks.data_ptr(), int(nchunks), _stream())

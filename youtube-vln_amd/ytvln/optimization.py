@@ -9,14 +9,16 @@ arenas, and a whole step is one HIP kernel launch per (param-group, step-count) 
 tensor x 541 tensors.  The flat gradient arena is also what the data-parallel all-reduce buckets (ytvln/distributed.py).
 
 Beyond the reference (it has no gradient clipping): two plain attributes, `optimizer.max_grad_norm` and `optimizer.skip_nonfinite`, bound
-the global gradient norm inside the step, and `optimizer.trust_ratio` switches the update to LAMB's layer-wise trust ratio -- see the
-`AdamW` docstring.
+the global gradient norm inside the step, `optimizer.trust_ratio` switches the update to LAMB's layer-wise trust ratio, and
+`optimizer.ema_decay` keeps an exponential moving average of the weights in a shadow arena -- see the `AdamW` docstring.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import numbers
 import struct
+from collections import OrderedDict
 from typing import Dict, List
 
 import torch
@@ -142,7 +144,26 @@ class AdamW(Optimizer):
         orders.  A plain attribute like the two above (anything but a bool raises ValueError when the step is taken), not in state_dict();
         with False the decay stays after the update and a step launches exactly what it always launched.  Baked into a captured step like
         the clip settings; its small buffers come from the first eager step with it on or from `lamb_buffers()`.  `trust_ratios()` is a
-        device view [tensors in arena order, 4] of the last step's rows [||p||, ||r||, trust, 0]."""
+        device view [tensors in arena order, 4] of the last step's rows [||p||, ||r||, trust, 0].
+
+    ema_decay (attribute, default None): a number strictly inside (0, 1) keeps an exponential moving average of the weights (timm's
+        ModelEmaV2) in a shadow arena with the offsets of the parameter arena: the shadow starts as a copy of the weights, and behind the
+        update launches of every chunk table one ytvln_ema_update applies e = fma(w, p - e, e) in fp32 to the parameters the update just
+        wrote (12 bytes per parameter, a launch of its own; no host synchronisation, no atomics).  w = float32(1 - decay_eff) is computed
+        on the host in double and travels through slot 6 of the per-class hyper record, so `ema_decay` and `ema_warmup` may change
+        between replays of a captured step; only on / off is baked into a capture (`prepare_replay()` raises when it differs).
+    ema_warmup (attribute, default False): True gives decay_eff = min(ema_decay, (1 + n) / (10 + n)), n = `ema_updates`.
+    ema_updates (attribute): the host count n of EMA updates taken.  Like `state[p]["step"]` it advances on a step the device decides
+        to skip (skip_nonfinite): the host cannot know the decision without a sync; the shadow itself is left untouched by such a step.
+    All three are plain attributes: not constructor arguments, not in `param_groups` / `defaults` / `state_dict()`.  A bool, a NaN or a
+    value outside (0, 1) for ema_decay, or anything but a bool for ema_warmup, raises ValueError when the step is taken.  With ema_decay =
+    None a step launches exactly what it always launched and nothing is allocated.  The shadow (`ema_buffers()`, created by the first eager
+    step with the feature on) survives an arena rebuild: members that had a shadow keep it, new members start from their current value;
+    parameters that never receive a gradient have none -- their EMA is the parameter itself.  Every data-parallel rank computes the same
+    shadow: nothing is exchanged.  `ema_parameters()` maps parameters to their shadow views, `ema_state_dict(model)` is the model file with
+    the shadow weights, `swap_ema()` / `with optimizer.ema_weights():` exchange weights and shadow in place for evaluation (views, arena
+    slots and captured graphs stay valid; stepping while swapped raises RuntimeError), `ema_checkpoint(model)` / `load_ema(state, model)`
+    carry the shadow through checkpoints (ytvln.utils_init.save_model, ytvln.vilbert_init.restore_checkpoint)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
         if lr < 0.0:
@@ -165,6 +186,12 @@ class AdamW(Optimizer):
         self._captured_clip = False  # the clipping settings recorded into the last captured step (False: nothing captured yet)
         self.trust_ratio = False    # LAMB layer-wise trust ratio (class docstring); a plain attribute, never part of state_dict()
         self._captured_lamb = None  # trust_ratio as recorded into the last captured step (None: nothing captured yet)
+        self.ema_decay = None       # EMA of the weights (class docstring); plain attributes, never part of state_dict()
+        self.ema_warmup = False
+        self.ema_updates = 0        # EMA updates taken (host count; advances on a device-skipped step as state[p]["step"] does)
+        self._captured_ema = None   # feature on / off as recorded into the last captured step (None: nothing captured yet)
+        self._ema_swapped = False   # swap_ema(): the parameter arena currently holds the shadow weights
+        self._ema_carry = {}        # id(param) -> shadow values waiting for the next arena (rebuild, load_ema)
 
     # ---- arena management -----------------------------------------------------------------------------------------
     def _members(self):
@@ -205,10 +232,13 @@ class AdamW(Optimizer):
                 p.grad = flat["g"][o:o + n].view(p.shape)
                 st["exp_avg"] = flat["m"][o:o + n].view(p.shape)
                 st["exp_avg_sq"] = flat["v"][o:o + n].view(p.shape)
+        self._stash_ema(old)
         self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None, partials=None, clip=None,
-                           lamb=None)
+                           lamb=None, ema=None)
         self._launch = None
         del old
+        if self._ema_carry and self.ema_decay is not None and not torch.cuda.is_current_stream_capturing():
+            self.ema_buffers()      # a shadow existed (or was loaded) and the feature is on: it moves into the new arena at once
         # let the weight-gradient GEMMs write straight into the gradient arena and the packed projections alias the
         # parameter arena: every member parameter carries its slot (ytvln.ops.ArenaSlot)
         self._written = set()
@@ -383,7 +413,173 @@ class AdamW(Optimizer):
         ops.lamb_stage2(a["p"], a["m"], a["v"], c["table"], c["n"], c["hyper"], trust, c["rec_tensor"], clip, p_bf16=a["pb"])
         a["lamb_stepped"] = True
 
+    # ---- EMA of the weights --------------------------------------------------------------------------------------------
+    def ema_setting(self):
+        """None with the feature off, else (ema_decay as a float, ema_warmup).  Raises ValueError for an ema_decay that is not a real number
+        strictly inside (0, 1) and for an ema_warmup that is not a bool."""
+        if not isinstance(self.ema_warmup, bool):
+            raise ValueError(f"ema_warmup must be True or False, got {self.ema_warmup!r}")
+        d = self.ema_decay
+        if d is None:
+            return None
+        if isinstance(d, bool) or not isinstance(d, numbers.Real):
+            raise ValueError(f"ema_decay must be None or a number strictly inside (0, 1), got {d!r}")
+        d = float(d)
+        if not 0.0 < d < 1.0:          # (also a NaN)
+            raise ValueError(f"ema_decay must be strictly inside (0, 1), got {d!r}")
+        return d, self.ema_warmup
+
+    def ema_weight(self, n=None) -> float:
+        """The weight w of the next EMA update, e += w (p - e): float32(1 - decay_eff), decay_eff = min(decay, (1 + n) / (10 + n)) with
+        warm-up and `decay` without, computed in double and rounded once to fp32 (returned as a Python float holding that fp32 value);
+        n = `ema_updates` unless given.  0.0 with the feature off."""
+        setting = self.ema_setting()
+        if setting is None:
+            return 0.0
+        decay, warm = setting
+        n = self.ema_updates if n is None else int(n)
+        if warm:
+            decay = min(decay, (1.0 + n) / (10.0 + n))
+        return struct.unpack("<f", struct.pack("<f", 1.0 - decay))[0]
+
+    def _stash_ema(self, arena):
+        """Before `arena` is dropped: keep views of its shadow per parameter for the arena that replaces it."""
+        if arena is not None and arena.get("ema") is not None:
+            for pid, (o, n) in arena["index"].items():
+                self._ema_carry[pid] = arena["ema"][o:o + n]
+
+    def ema_buffers(self):
+        """The shadow arena: fp32, the size and offsets of the parameter arena.  Created on first use -- only with the feature on -- as a copy
+        of the parameter arena at that moment; shadow values carried over from a previous arena or handed to load_ema() replace the copy for
+        their parameters.  Not part of state_dict.  None before the arena exists."""
+        a = self._arena
+        if a is None:
+            return None
+        if a["ema"] is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ema_decay was switched on after the last eager step: take one eager step with it on (or call "
+                                   "ema_buffers()) before capturing, so that its buffer does not live in a graph's pool")
+            with torch.no_grad():
+                a["ema"] = a["p"].clone()
+        if self._ema_carry:
+            with torch.no_grad():
+                for pid in [pid for pid in self._ema_carry if pid in a["index"]]:
+                    o, n = a["index"][pid]
+                    t = self._ema_carry.pop(pid)
+                    if t.numel() != n:
+                        raise RuntimeError(f"EMA shadow of {t.numel()} elements for a parameter of {n}")
+                    a["ema"][o:o + n].copy_(t.reshape(-1))
+            self._ema_carry.clear()          # what is left belongs to no member: should it join later, it starts from its current value
+        return a["ema"]
+
+    def _ema_if_any(self):
+        """The shadow arena when it exists or the feature is on (then created), else None: reading never allocates with the feature off."""
+        a = self._arena
+        if a is None or (a["ema"] is None and self.ema_setting() is None):
+            return None
+        return self.ema_buffers()
+
+    def _ema_members(self):
+        a = self._arena
+        return [] if a is None else [p for g in self.param_groups for p in g["params"] if id(p) in a["index"]]
+
+    def ema_parameters(self):
+        """{parameter: its view into the shadow arena} for every arena member (parameters that never received a gradient are absent:
+        their EMA is the parameter itself).  Empty before the arena exists.  While swapped (swap_ema) the views hold the training weights."""
+        e = self._ema_if_any()
+        out = {}
+        if e is not None:
+            for p in self._ema_members():
+                o, n = self._arena["index"][id(p)]
+                out[p] = e[o:o + n].view(p.shape)
+        return out
+
+    def ema_state_dict(self, model):
+        """OrderedDict with exactly the keys of `model.state_dict()`: cloned shadow values for arena members, cloned current values for
+        everything else (parameters without a gradient, buffers) -- the file to evaluate or ship."""
+        if self._ema_swapped:
+            raise RuntimeError("ema_state_dict(): the weights are swapped with the shadow (swap_ema / ema_weights): swap back first")
+        e = self._ema_if_any()
+        index = {} if self._arena is None else self._arena["index"]
+        out = OrderedDict()
+        for k, v in model.state_dict(keep_vars=True).items():
+            rng = index.get(id(v))
+            out[k] = v.detach().clone() if (e is None or rng is None) else e[rng[0]:rng[0] + rng[1]].view(v.shape).clone()
+        return out
+
+    def ema_checkpoint(self, model):
+        """The value of the checkpoint key `ytvln_ema_state` (None with the feature off): {"decay", "warmup", "updates", "shadow": {name
+        in model.state_dict(): cloned shadow tensor of that arena member}}."""
+        setting = self.ema_setting()
+        if setting is None:
+            return None
+        if self._ema_swapped:
+            raise RuntimeError("ema_checkpoint(): the weights are swapped with the shadow (swap_ema / ema_weights): swap back first")
+        e = self.ema_buffers()
+        shadow = OrderedDict()
+        if e is not None:
+            for k, v in model.state_dict(keep_vars=True).items():
+                rng = self._arena["index"].get(id(v))
+                if rng is not None:
+                    shadow[k] = e[rng[0]:rng[0] + rng[1]].view(v.shape).clone()
+        for k, v in model.state_dict(keep_vars=True).items():          # loaded, not yet adopted (no step since): carried through
+            if k not in shadow and id(v) in self._ema_carry:
+                shadow[k] = self._ema_carry[id(v)].detach().clone().view(v.shape)
+        return {"decay": setting[0], "warmup": setting[1], "updates": int(self.ema_updates), "shadow": shadow}
+
+    def load_ema(self, state, model):
+        """Take the shadow and the update count of a checkpoint's `ytvln_ema_state` (names are those of `model.state_dict()`).  The tensors
+        stay pending until the shadow arena exists: ema_buffers() adopts them (the first step with the feature on; at once when the shadow
+        is already there).  `ema_decay` / `ema_warmup` are settings like max_grad_norm: they come from the attributes, not from the file."""
+        if self._ema_swapped:
+            raise RuntimeError("load_ema(): the weights are swapped with the shadow (swap_ema / ema_weights): swap back first")
+        named = model.state_dict(keep_vars=True)
+        for k, t in state["shadow"].items():
+            if k not in named:
+                raise KeyError(f"load_ema: the model has no tensor named {k!r}")
+            if tuple(t.shape) != tuple(named[k].shape):
+                raise RuntimeError(f"load_ema: {k}: shadow of shape {tuple(t.shape)} for a tensor of shape {tuple(named[k].shape)}")
+            self._ema_carry[id(named[k])] = t.detach().to(dtype=torch.float32)
+        self.ema_updates = int(state["updates"])
+        if self._arena is not None and self._arena["ema"] is not None:
+            self.ema_buffers()
+
+    def swap_ema(self):
+        """Exchange the parameter arena and the shadow in place, ytvln_ema_swap over every launch class on the current stream; the bf16
+        weight copy (bf16_arena()) is refreshed by the same pass.  Only contents move: parameter views, arena slots and captured graphs
+        stay valid.  Until the next swap_ema() the optimizer refuses to step."""
+        a = self._arena
+        if a is None or self._launch is None or a["ema"] is None:
+            raise RuntimeError("swap_ema(): no step has been taken with ema_decay set")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("swap_ema() is an eager operation: not inside a capture")
+        self.ema_buffers()
+        for c in self._launch:
+            ops.ema_swap(a["p"], a["ema"], c["table"], c["n"], p_bf16=a["pb"])
+        self._ema_swapped = not self._ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with optimizer.ema_weights():` -- the model computes with the shadow weights inside the block (swap_ema() in and back out)."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def _not_swapped(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what}: the weights are swapped with their EMA shadow (swap_ema / ema_weights); swap back before training on")
+
     def _update(self, table, n, hyper, cls=None):
+        a = self._arena
+        # the shadow starts as the weights BEFORE the first update it follows: created (first use) ahead of the update launches
+        shadow = self.ema_buffers() if self.ema_setting() is not None else None
+        self._update_launches(table, n, hyper, cls)
+        if shadow is not None:          # a launch of its own behind the update: element-wise, so any cut of the table will do
+            ops.ema_update(a["p"], shadow, table, n, hyper, self.clip_buffers()[1] if self.clip_settings() is not None else None)
+
+    def _update_launches(self, table, n, hyper, cls=None):
         a = self._arena
         if self.lamb_setting():
             if cls is None or table is not cls["table"]:
@@ -458,17 +654,20 @@ class AdamW(Optimizer):
         """torch's loader replaces `state[p]["exp_avg"/"exp_avg_sq"]` with fresh tensors: drop the arenas so the next step rebuilds
         them and re-adopts the LOADED moments (otherwise the kernel would keep updating the old arena while state_dict()
         serialised the stale loaded tensors)."""
+        self._not_swapped("load_state_dict()")
         super().load_state_dict(state_dict)
         # parameters / gradients keep viewing the old arenas (still valid memory) until the rebuild copies them over
         if self._arena is not None:
             self._written.clear()
+        self._stash_ema(self._arena)          # the EMA shadow is not optimizer state of the file: it moves into the next arena
         self._arena = None
         self._launch = None
 
     # ---- the step -------------------------------------------------------------------------------------------------
     def _upload_hyper(self):
-        """Host -> device upload of (beta1, beta2, eps, step_size, lr, bias correction) for every launch class and advance of the step
-        counters.  Eager by design: under hipGraph replay (`capturing=True` steps) this is the only per-step host work."""
+        """Host -> device upload of (beta1, beta2, eps, step_size, lr, bias correction, EMA weight) for every launch class and advance of
+        the step counters.  Eager by design: under hipGraph replay (`capturing=True` steps) this is the only per-step host work."""
+        ema_w = self.ema_weight()           # 0 with the EMA off
         for c in self._launch:
             g = self.param_groups[c["group"]]
             b1, b2 = g["betas"]
@@ -483,12 +682,15 @@ class AdamW(Optimizer):
             host = c["ring"][k]
             host[0], host[1], host[2], host[3], host[4] = b1, b2, g["eps"], step_size, g["lr"]
             host[5] = bias              # read by the LAMB launches only (trust_ratio)
+            host[6] = ema_w             # read by ytvln_ema_update only (ema_decay)
             c["hyper"].copy_(host, non_blocking=True)
             c["events"][k] = torch.cuda.Event()
             c["events"][k].record()
             c["step"] = t
             for p in c["params"]:
                 self.state[p]["step"] = t
+        if self.ema_decay is not None:
+            self.ema_updates += 1
 
     def _launch_kernels(self):
         if self.clip_settings() is not None:      # norm of what the update reads -> coefficient -> clip-aware update, all in stream order
@@ -496,6 +698,7 @@ class AdamW(Optimizer):
         if torch.cuda.is_current_stream_capturing():
             self._captured_clip = self.clip_settings()
             self._captured_lamb = self.lamb_setting()
+            self._captured_ema = self.ema_setting() is not None
         self.launch_classes()
 
     @torch.no_grad()
@@ -506,6 +709,8 @@ class AdamW(Optimizer):
                 loss = closure()
         self.clip_settings()              # invalid max_grad_norm: ValueError before anything is exchanged, launched or recorded
         self.lamb_setting()               # (and an invalid trust_ratio)
+        self.ema_setting()                # (and an invalid ema_decay / ema_warmup)
+        self._not_swapped("step()")
         if torch.cuda.is_current_stream_capturing():
             # inside a hipGraph capture of a whole training step: only the device work is recorded; the caller uploads the
             # hyper-parameters eagerly before every replay (`prepare_replay()`).  The arena must already exist.
@@ -603,11 +808,13 @@ class AdamW(Optimizer):
 
     def launch_classes(self):
         """The update of every launch class over its whole chunk table, on the current stream: the form the LAMB update (trust_ratio) needs."""
+        self._not_swapped("launch_classes()")
         for c in self._launch:
             self._update(c["table"], c["n"], c["hyper"], c)
 
     def launch_tables(self, tables):
         """The fused AdamW kernels of one group, on the current stream (hyper-parameters come from prepare_replay())."""
+        self._not_swapped("launch_tables()")
         for ci, table, n in tables:
             self._update(table, n, self._launch[ci]["hyper"])
 
@@ -621,6 +828,7 @@ class AdamW(Optimizer):
 
     def capture_update(self):
         """Inside a capture: record the fused AdamW kernels (hyper-parameters come from prepare_replay())."""
+        self._not_swapped("capture_update()")
         if not torch.cuda.is_current_stream_capturing():
             raise RuntimeError("capture_update() is only meaningful while capturing a hipGraph")
         self._written.clear()
@@ -632,12 +840,17 @@ class AdamW(Optimizer):
 
     def prepare_replay(self):
         """Call before each replay of a captured training step (after scheduler.step() set the new learning rate).  The captured step
-        carries the clipping settings and trust_ratio it was recorded with: raises if one of them changed since."""
+        carries the clipping settings, trust_ratio and EMA on / off it was recorded with: raises if one of them changed since (the EMA's
+        decay and warm-up travel by value and may change freely)."""
+        self._not_swapped("prepare_replay()")
         if self._captured_clip is not False and self.clip_settings() != self._captured_clip:
             raise RuntimeError(f"max_grad_norm / skip_nonfinite changed since the step was captured (captured {self._captured_clip}, now "
                                f"{self.clip_settings()}): the graph holds the old launches -- capture the step again")
         if self._captured_lamb is not None and self.lamb_setting() != self._captured_lamb:
             raise RuntimeError(f"trust_ratio changed since the step was captured (captured {self._captured_lamb}, now {self.trust_ratio}): "
+                               "the graph holds the old launches -- capture the step again")
+        if self._captured_ema is not None and (self.ema_setting() is not None) != self._captured_ema:
+            raise RuntimeError(f"ema_decay was switched {'off' if self._captured_ema else 'on'} since the step was captured: "
                                "the graph holds the old launches -- capture the step again")
         self._upload_hyper()
 

@@ -284,11 +284,15 @@ def save_model(model_save_path, save_name, logger, model, optimizer, scheduler, 
     opt_state = {"param_groups": live["param_groups"],
                  "state": {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                            for i, st in live["state"].items()}}
-    # the four keys are the reference's; `ytvln_rng_state` (dropout / masking stream position) is an extra the reference ignores
-    torch.save({"model_state_dict": {k: v.detach().clone() for k, v in net.state_dict().items()},
-                "optimizer_state_dict": opt_state, "scheduler_state_dict": scheduler.state_dict(), "epoch": epoch,
-                "ytvln_rng_state": ops.DropoutState.get_state()},
-               get_model_path(model_save_path, save_name))
+    # the four keys are the reference's; `ytvln_rng_state` (dropout / masking stream position) is an extra the reference ignores, and so is
+    # `ytvln_ema_state` (the EMA shadow of the weights), present only when the optimizer keeps one
+    ckpt = {"model_state_dict": {k: v.detach().clone() for k, v in net.state_dict().items()},
+            "optimizer_state_dict": opt_state, "scheduler_state_dict": scheduler.state_dict(), "epoch": epoch,
+            "ytvln_rng_state": ops.DropoutState.get_state()}
+    ema = optimizer.ema_checkpoint(net) if hasattr(optimizer, "ema_checkpoint") else None
+    if ema is not None:
+        ckpt["ytvln_ema_state"] = ema
+    torch.save(ckpt, get_model_path(model_save_path, save_name))
 
 
 def delete_model(model_save_path, save_name):

@@ -38,7 +38,8 @@ def build_scheduler(args, optimizer, steps_per_epoch: int):
 def restore_checkpoint(path, model, optimizer, scheduler, logger=None) -> int:
     """Load whatever of {model_state_dict, optimizer_state_dict, scheduler_state_dict, epoch} the file holds
     (vilbert_init.py:44-64); returns the epoch to continue from.  A missing file is reported, not fatal, like the reference.
-    Files written by this repo also carry the dropout / masking stream position (`ytvln_rng_state`)."""
+    Files written by this repo also carry the dropout / masking stream position (`ytvln_rng_state`) and, when the run kept an EMA of the
+    weights, its shadow (`ytvln_ema_state`)."""
     path = Path(path)
     say = logger.info if logger else (lambda *_: None)
     say(f"resume the training model from {path}")
@@ -56,6 +57,9 @@ def restore_checkpoint(path, model, optimizer, scheduler, logger=None) -> int:
     if "ytvln_rng_state" in ckpt:
         p0 = next(net.parameters(), None)          # the mask stream lives on the model's device, which need not be the current one
         ops.DropoutState.set_state(ckpt["ytvln_rng_state"], device=p0.device if (p0 is not None and p0.is_cuda) else None)
+    if "ytvln_ema_state" in ckpt and hasattr(optimizer, "load_ema"):          # the EMA shadow of the weights (ytvln.optimization.AdamW)
+        optimizer.load_ema(ckpt["ytvln_ema_state"], net)
+        say("load ytvln_ema_state...")
     return ckpt["epoch"] + 1 if "epoch" in ckpt else 0
 
 
@@ -67,6 +71,10 @@ def get_optimization(args, model, train_data_loader_length, logger):
     optimizer.skip_nonfinite = bool(getattr(args, "skip_nonfinite_grads", False))
     if hasattr(args, "lamb"):                 # LAMB layer-wise trust ratio (beyond the reference as well); validated when a step is taken
         optimizer.trust_ratio = args.lamb
+    if hasattr(args, "ema_decay"):            # EMA of the weights (beyond the reference as well); validated when a step is taken
+        optimizer.ema_decay = args.ema_decay
+    if hasattr(args, "ema_warmup"):
+        optimizer.ema_warmup = args.ema_warmup
     scheduler = build_scheduler(args, optimizer, train_data_loader_length)
     start_epoch = 0
     if getattr(args, "resume", False):
