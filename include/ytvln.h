@@ -298,6 +298,22 @@ int ytvln_attn_fwd_pair(const ytvln_attn_problem* a, const ytvln_attn_problem* b
                         const int64_t* rng, void* stream);
 int ytvln_attn_bwd_pair(const ytvln_attn_problem* a, const ytvln_attn_problem* b, int N, int heads, int d, float scale,
                         const int64_t* rng, void* stream);
+/* The fp32 backward with a workspace for the stored-dS form (option ATTN_W1 bit 3): the dK/dV kernel writes every 32x32 block of dS it forms
+ * to `workspace` and the dQ kernel only contracts those blocks with K instead of recomputing them; delta comes from a small pass of its own
+ * in front.  dq, dk, dv and delta are bit-identical to ytvln_attn_bwd_f32 / ytvln_attn_bwd_pair.
+ * ytvln_attn_bwd_workspace_elems: pure host code -- the floats a launch of that shape uses, N heads ceil32(Tq) ceil32(Tk) summed over its
+ * problems (Tq_b = Tk_b = 0: one problem), or 0 when the launch would not take the form (bit 3 of ATTN_W1 clear, d not 64 / 128, a sequence
+ * longer than 512, or a launch whose dK/dV runs in the wave-pair form).  `workspace` (16-byte aligned) is scratch: written and read inside the
+ * call's own kernels, in stream order.  NULL, or workspace_elems below that count: the recomputing kernels run, exactly as through the entry
+ * points above -- never an error. */
+int64_t ytvln_attn_bwd_workspace_elems(int N, int heads, int d, int Tq_a, int Tk_a, int Tq_b, int Tk_b);
+int ytvln_attn_bwd_ws_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                          const float* mask, const float* ctx, const float* dctx, int64_t ldo, const float* lse,
+                          float* delta, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, int N,
+                          int heads, int Tq, int Tk, int d, float scale, float p_drop, const int64_t* rng, int64_t site,
+                          float* workspace, int64_t workspace_elems, void* stream);
+int ytvln_attn_bwd_pair_ws(const ytvln_attn_problem* a, const ytvln_attn_problem* b, int N, int heads, int d, float scale,
+                           const int64_t* rng, float* workspace, int64_t workspace_elems, void* stream);
 /* The same attention for the bf16-resident path (BASELINE configs[4]): in the problem records q, k, v, ctx, ctx_in, dctx, dq, dk, dv point to
  * BF16 tensors (leading dimensions in elements), mask / lse / lse_in / delta stay fp32; every contraction runs on v_mfma_f32_32x32x16_bf16
  * with fp32 accumulation and fp32 softmax, the transposed operands (V^T.P^T, K^T.dS^T, Q^T.dS, dO^T.P) are gathered from the row-major LDS

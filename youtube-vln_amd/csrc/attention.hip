@@ -48,6 +48,7 @@ struct AttnArgs {
     float scale, p_drop;
     const int64_t* rng; int64_t site;
     int dsplit;        // 1: single-tile two-wave workgroups run the d-split form (the launch reserved the 4 KB exchange buffer)
+    float* ds;         // stored-dS backward (attn_bwd_dq_ds_body): this problem's dS blocks, [n][head][query tile][key tile][32 queries][32 keys]
 };
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -1179,7 +1180,11 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
 //     wait Q(t)    S = Q.K^T                       wait dO(t)    dP = dO.V^T         P, keep, dS
 //     dK += dS^T.Q   -> DMA Q(t+1)  (travels under the next matmul)      dV += (P o keep)^T.dO   -> DMA dO(t+1)  (travels under the next S)
 // Same arithmetic, same order as attn_bwd_dkv_body: bit-identical results.
-template <int DP, bool DROP>
+// STORE: the stored-dS backward (attn_bwd_dq_ds_body below) -- every finished dS block also goes to a.ds.  The wave holds it with lane = key and
+// register r = query krow(r, half), so each of the 16 dword stores writes two whole 128-byte rows of the [query][key] block.  The stores count on
+// the wave's vmcnt like the LDS-DMA pieces issued after them; they are the OLDEST entries when the next tile waits for Q(t+1) with DP/8 left in
+// flight, and loads retire in order among themselves, so that wait still covers Q(t+1) whatever order the stores complete in.
+template <int DP, bool DROP, bool STORE = false>
 __device__ __forceinline__ void attn_bwd_dkv_w1_body(const AttnArgs& a, const int bx, const int h, const int n) {
     constexpr int TS = 32 * DP, NJ = DP / 32;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1228,6 +1233,10 @@ __device__ __forceinline__ void attn_bwd_dkv_w1_body(const AttnArgs& a, const in
     DropKey key = {0, 0, 0, 0};
     uint32_t thr = 0; float ik = 1.f;
     if (DROP) { key = make_drop_key(a.rng, a.site); thr = drop_threshold(a.p_drop); ik = 1.0f / (1.0f - a.p_drop); }
+    // STORE: block (query tile t, key tile bx) of this (pair, head) lies at dsb + t * dstep; the lane's part of the address is a constant
+    const int dstep = ((a.Tk + 31) >> 5) * 1024;
+    float* __restrict__ dsb = STORE ? a.ds + (((int64_t)n * a.heads + h) * nqt * ((a.Tk + 31) >> 5) + bx) * 1024 : nullptr;
+    const int dlane = 128 * half + l31;          // row krow(0, half) = 4 * half, column l31
 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     // (the last tile is peeled: no conditional DMA issue inside the loop -- control flow there costs register shuffles of both accumulators)
@@ -1258,6 +1267,11 @@ __device__ __forceinline__ void attn_bwd_dkv_w1_body(const AttnArgs& a, const in
                 dS[r] = p * (dp - dsv[u]);
             }
         }
+        if constexpr (STORE) {          // whole blocks: keys / queries past the end carry exact zeros (mask -inf / lse +inf)
+            float* __restrict__ blk = dsb + (int64_t)t * dstep;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) blk[dlane + 32 * ((r & 3) + 8 * (r >> 2))] = dS[r];
+        }
         const bool short_tile = YT_ATTN_SHORT_TILE && DP == 128 && !more && a.Tq - i0 <= 16;          // a 16-row last tile: see mma_regs_rows
         if (short_tile) mma_regs_rows<DP, W1_PIPE, NoFill, 8>(accK, dS, Qs, lo);
         else mma_regs_rows<DP, W1_PIPE>(accK, dS, Qs, lo);          // dK += dS^T . Q
@@ -1272,6 +1286,85 @@ __device__ __forceinline__ void attn_bwd_dkv_w1_body(const AttnArgs& a, const in
     tile(std::false_type{}, nqt - 1);
     store_rows<DP>(accV, a.dv, a.lddv, (int64_t)n * a.Tk, k0, a.Tk, col0, a.d, l31, half, 1.0f);
     store_rows<DP>(accK, a.dk, a.lddk, (int64_t)n * a.Tk, k0, a.Tk, col0, a.d, l31, half, a.scale);
+}
+
+// ---- stored-dS backward (option ATTN_W1 bit 3): the dK/dV wave above has every dS block in registers, so it writes them out once and the dQ
+// kernel below only contracts them with K -- 64 of the 192 matrix instructions attn_bwd_dq_w1_body spends per (query tile, key tile) pair, no
+// exp / mask / dropout hash, no V stream, no Q / dO / O fragments.  Order on the stream: delta pass -> dK/dV (reads delta, writes dS) -> dQ.
+// The stored bits are the ones attn_bwd_dq_w1_body recomputes (the same products summed in the same order with the operand roles swapped, the
+// same elementwise chain), and the contraction below is its mma_regs_rows in its key-tile order: dq, dk, dv and delta are bit-identical to the
+// recomputing form (tests/test_attn_stored_ds_gpu.py).
+//
+// delta[n,h,q] = sum_c dctx . ctx: the prologue of attn_bwd_dq_w1_body as a kernel of its own (the same fragments, the same chain of sums)
+template <int DP>
+__device__ __forceinline__ void attn_bwd_delta_body(const AttnArgs& a, const int bx, const int h, const int n) {
+    const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+    const int qi = bx * 32 + l31;
+    const bool qvalid = qi < a.Tq;
+    const int col0 = h * a.d;
+    const int64_t sidx = ((int64_t)n * a.heads + h) * a.Tq + qi;
+    float Gr[DP / 2], Cr[DP / 2];
+    load_rowfrag_raw<DP>(Gr, a.dctx, a.ldo, (int64_t)n * a.Tq, qi, a.Tq, col0, half);
+    load_rowfrag_raw<DP>(Cr, a.ctx, a.ldo, (int64_t)n * a.Tq, qi, a.Tq, col0, half);
+    float acc = 0.f;
+#pragma unroll
+    for (int s4 = 0; s4 < DP / 2; s4 += 4) acc += (Cr[s4] * Gr[s4] + Cr[s4 + 1] * Gr[s4 + 1]) + (Cr[s4 + 2] * Gr[s4 + 2] + Cr[s4 + 3] * Gr[s4 + 3]);
+    const float dl = acc + __shfl_xor(acc, 32, 64);
+    if (qvalid && half == 0) a.delta_out[sidx] = dl;
+}
+
+// dQ from the stored blocks: ONE wave per (pair, head, 32-query tile).  LDS: one K tile (W1Stream) | one dS block, 20 KB at d = 128, and 184 + 64
+// registers: two waves share a SIMD and cover each other's fetches and prologues (a second K buffer, K(t+1) under the contraction of tile t, costs
+// 36 KB, i.e. one wave per SIMD with nothing under its prologue: measured slower at every site, LABNOTES "Attention backward from stored dS
+// blocks").  The blocks of one query tile are consecutive in the workspace, i.e. a row-major [key tiles x 32][32] matrix that a W1Stream<32> walks:
+// every vector-memory operation of this kernel is an LDS-DMA piece (K: DP/8 per tile, dS: 4), so the wave's own vmcnt is the only wait and hipcc
+// has no register load to drain the queue for.  A block arrives in the Tile<32> layout (granule g of row r at position g ^ (r & 7)); the lane
+// reads its own query's row, keys krow(r, half), as four ds_read_b128 -- the A operand of mma_regs_rows as attn_bwd_dq_w1_body holds it.
+// Per key tile t:     wait K(t), dS(t)     dS(t) -> registers     -> DMA dS(t+1)     dQ += dS(t).K(t)     -> DMA K(t+1)
+template <int DP>
+__device__ __forceinline__ void attn_bwd_dq_ds_body(const AttnArgs& a, const int bx, const int h, const int n) {
+    constexpr int TS = 32 * DP, NJ = DP / 32;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* __restrict__ Ks = smem;
+    float* __restrict__ Ds = smem + TS;
+    const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+    const int q0 = bx * 32;
+    const int col0 = h * a.d;
+    const int ntiles = (a.Tk + 31) >> 5, nqt = (a.Tq + 31) >> 5;
+    const LaneOff lo = make_lane_off<DP>(l31, half);
+    W1Stream<DP> ks;
+    W1Stream<32> ds;
+    ks.init(a.k + (int64_t)n * a.Tk * a.ldk + col0, Ks, (int)a.ldk, a.Tk, lane);
+    ds.init(a.ds + ((((int64_t)n * a.heads + h) * nqt + bx) * ntiles) * 1024, Ds, 32, ntiles * 32, lane);
+    int doff[4];          // this lane's query row, granules 2g + half
+#pragma unroll
+    for (int g = 0; g < 4; ++g) doff[g] = l31 * 32 + 4 * ((2 * g + half) ^ (l31 & 7));
+    ks.issue(0);
+    ds.issue(0);
+    f32x16 dQ[NJ];
+#pragma unroll
+    for (int c = 0; c < NJ; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dQ[c][r] = 0.f;
+    for (int t = 0; t < ntiles; ++t) {
+        const int j0 = t * 32;
+        const bool more = t + 1 < ntiles;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // K(t) and dS(t): everything this wave has asked for
+        float dS[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 x = lds4(Ds + doff[g]);
+            dS[4 * g] = x.x; dS[4 * g + 1] = x.y; dS[4 * g + 2] = x.z; dS[4 * g + 3] = x.w;
+        }
+        lds_reads_done();
+        if (more) ds.issue(j0 + 32);
+        __builtin_amdgcn_sched_barrier(0);
+        if (YT_ATTN_SHORT_TILE && DP == 128 && a.Tk - j0 <= 16) mma_regs_rows<DP, W1_PIPE, NoFill, 8>(dQ, dS, Ks, lo);          // a 16-row last tile: see mma_regs_rows
+        else mma_regs_rows<DP, W1_PIPE>(dQ, dS, Ks, lo);
+        lds_reads_done();
+        if (more) ks.issue(j0 + 32);
+    }
+    store_rows<DP>(dQ, a.dq, a.lddq, (int64_t)n * a.Tq, q0, a.Tq, col0, a.d, l31, half, a.scale);
 }
 
 // diagnostic: materialise attention_probs (reference returns them when output_all_attention_masks=True)
@@ -1338,6 +1431,13 @@ template <int DP, bool DROP>
 __global__ __launch_bounds__(64) void attn_bwd_dkv_w1_kernel(const AttnLaunch b) { YT_ATTN_DECODE((attn_bwd_dkv_w1_body<DP, DROP>(a, bx, h, n))); }
 template <int DP, bool DROP, int STAGES>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnLaunch b) { YT_ATTN_DECODE((attn_bwd_dkv_body<DP, DROP, STAGES>(a, bx, h, n))); }
+// the stored-dS backward
+template <int DP>
+__global__ __launch_bounds__(64) void attn_bwd_delta_kernel(const AttnLaunch b) { YT_ATTN_DECODE((attn_bwd_delta_body<DP>(a, bx, h, n))); }
+template <int DP, bool DROP>
+__global__ __launch_bounds__(64) void attn_bwd_dkv_w1_ds_kernel(const AttnLaunch b) { YT_ATTN_DECODE((attn_bwd_dkv_w1_body<DP, DROP, true>(a, bx, h, n))); }
+template <int DP>
+__global__ __launch_bounds__(64) void attn_bwd_dq_ds_kernel(const AttnLaunch b) { YT_ATTN_DECODE((attn_bwd_dq_ds_body<DP>(a, bx, h, n))); }
 #undef YT_ATTN_DECODE
 // the biased forms: the two-wave / wave-pair bodies only (the one-wave kernels sit at their register limit and keep the mask row in registers)
 #define YT_ATTN_DECODE_B(BODY_CALL)                                                                            \
@@ -1498,7 +1598,30 @@ static int launch_fwd(AttnLaunchB& bb, int np, hipStream_t s) {
     return 0;
 }
 
-static int launch_bwd(AttnLaunchB& bb, int np, hipStream_t s) {
+// Whether an unbiased backward launch takes the one-wave dK/dV kernel (attn_bwd_dkv_w1_body; option ATTN_W1 bit 2 clear: always the wave-pair
+// form): unpadded fp32 heads, lse / delta rows staged by one wave, and at least two rounds of the 1024 wave slots (a 1.3-round launch -- 3 key
+// tiles x 448 heads -- pays for 2: there the pair form, whose workgroups are half as long, loses less; option ATTN_W1_DKV_ANY = 1 takes the
+// one-wave form regardless).  Pure host code, symmetric in the two problems.
+struct BwdShape { int np, N, heads, d, Tq[2], Tk[2]; };
+static bool dkv_w1_form(const BwdShape& sh) {
+    const int maxTq = std::max(sh.Tq[0], sh.np > 1 ? sh.Tq[1] : 0);
+    const int64_t w1_waves = (cdiv(sh.Tk[0], 32) + (sh.np > 1 ? cdiv(sh.Tk[1], 32) : 0)) * sh.heads * sh.N;
+    const int64_t w1_slots = sh.d == 128 ? 1024 : 2048;          // (d = 64: 17 KB of LDS and < 256 registers per wave -> two per SIMD)
+    const bool w1_fill = w1_waves * 100 >= cdiv(w1_waves, w1_slots) * w1_slots * 85;      // the last round at least ~85 % useful overall
+    return (opt(OPT_ATTN_W1) & 4) && (sh.d == 128 || sh.d == 64) && maxTq <= 512 && (w1_fill || opt(OPT_ATTN_W1_DKV_ANY));
+}
+// floats of dS workspace the stored-dS backward (attn_bwd_dq_ds_body) uses for problem i: whole 32x32 blocks
+static int64_t ds_elems(const BwdShape& sh, int i) { return (int64_t)sh.N * sh.heads * cdiv(sh.Tq[i], 32) * cdiv(sh.Tk[i], 32) * 1024; }
+// ... and of the launch; 0: the launch does not take that form (option ATTN_W1 bit 3 clear, a shape its kernels are not built for, or a launch
+// whose dK/dV runs in the wave-pair form, which keeps no whole dS block in one wave)
+static int64_t stored_ds_elems(const BwdShape& sh) {
+    const int maxTk = std::max(sh.Tk[0], sh.np > 1 ? sh.Tk[1] : 0);
+    if (sh.N <= 0 || sh.heads <= 0 || sh.Tq[0] <= 0 || sh.Tk[0] <= 0 || (sh.np > 1 && (sh.Tq[1] <= 0 || sh.Tk[1] <= 0))) return 0;
+    if (!(opt(OPT_ATTN_W1) & 8) || maxTk > 512 || !dkv_w1_form(sh)) return 0;
+    return ds_elems(sh, 0) + (sh.np > 1 ? ds_elems(sh, 1) : 0);
+}
+
+static int launch_bwd(AttnLaunchB& bb, int np, hipStream_t s, float* ws = nullptr, int64_t ws_elems = 0) {
     AttnLaunch& b = bb.l;
     const bool biased = bb.bias[0].ptr || (np > 1 && bb.bias[1].ptr);          // (per launch, see launch_fwd)
     const AttnArgs& a0 = b.p[0];
@@ -1514,9 +1637,41 @@ static int launch_bwd(AttnLaunchB& bb, int np, hipStream_t s) {
         drop = drop || a.p_drop > 0.f;
         maxTq = std::max(maxTq, a.Tq); maxTk = std::max(maxTk, a.Tk);
     }
-    // delta[n,h,q] = sum_c dctx.ctx is produced by the dQ kernel's prologue (it owns the query rows) and read by the dK/dV kernel that
-    // follows it on the stream
+    // delta[n,h,q] = sum_c dctx.ctx is written before the dK/dV kernel reads it on the stream: by the dQ kernel's prologue (it owns the query
+    // rows) in the recomputing forms, by attn_bwd_delta_kernel in the stored-dS form
     for (int i = 0; i < np; ++i) b.p[i].delta_out = const_cast<float*>(b.p[i].delta);
+    BwdShape sh = {np, a0.N, a0.heads, a0.d, {b.p[0].Tq, np > 1 ? b.p[1].Tq : 0}, {b.p[0].Tk, np > 1 ? b.p[1].Tk : 0}};
+    // The stored-dS form (attn_bwd_dq_ds_body): delta pass -> one-wave dK/dV, which also writes its dS blocks -> a dQ kernel that only contracts
+    // them with K.  Taken when the caller brought the workspace (a missing or short one means the recomputing kernels below, not an error).
+    const int64_t ds_need = biased ? 0 : stored_ds_elems(sh);
+    if (ds_need > 0 && ws && ws_elems >= ds_need && ((uintptr_t)ws & 15) == 0) {
+        b.p[0].ds = ws;
+        if (np > 1) b.p[1].ds = ws + ds_elems(sh, 0);
+        const size_t lds_dq = (size_t)(32 * dp + 1024) * sizeof(float);
+        const size_t lds_dk = (size_t)(2 * 32 * dp + 2 * (int)cdiv(maxTq, 32) * 32) * sizeof(float);
+        int64_t total = 0;
+        auto by_query_tiles = [&]() {          // delta pass and dQ: a workgroup per 32 queries, the long-key direction first (as below)
+            if (np > 1 && b.p[1].Tk > b.p[0].Tk) swap_problems(bb);
+            b.gx0 = (int)cdiv(b.p[0].Tq, 32); b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tq, 32) : 1;
+            b.nb0 = b.gx0 * a0.heads * a0.N;
+            total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
+        };
+        by_query_tiles();
+        YT_REQUIRE(total < (1ll << 31), "attn_bwd: grid too large");
+        if (a0.d == 128) hipLaunchKernelGGL((attn_bwd_delta_kernel<128>), dim3((unsigned)total), dim3(64), 0, s, b);
+        else hipLaunchKernelGGL((attn_bwd_delta_kernel<64>), dim3((unsigned)total), dim3(64), 0, s, b);
+        if (np > 1 && b.p[1].Tq > b.p[0].Tq) swap_problems(bb);          // dK/dV: a workgroup per 32 keys, the long-query direction first (as below)
+        b.gx0 = (int)cdiv(b.p[0].Tk, 32); b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tk, 32) : 1;
+        b.nb0 = b.gx0 * a0.heads * a0.N;
+        total = (int64_t)b.nb0 + (np > 1 ? (int64_t)b.gx1 * a0.heads * a0.N : 0);
+        YT_REQUIRE(total < (1ll << 31), "attn_bwd: grid too large");
+        YT_W1(attn_bwd_dkv_w1_ds_kernel, lds_dk);
+        by_query_tiles();
+        if (a0.d == 128) hipLaunchKernelGGL((attn_bwd_dq_ds_kernel<128>), dim3((unsigned)total), dim3(64), lds_dq, s, b);
+        else hipLaunchKernelGGL((attn_bwd_dq_ds_kernel<64>), dim3((unsigned)total), dim3(64), lds_dq, s, b);
+        YT_LAUNCH_CHECK("attn_bwd (stored dS)");
+        return 0;
+    }
     if (np > 1 && b.p[1].Tk > b.p[0].Tk) swap_problems(bb);          // dQ workgroups walk key tiles: the long-key direction first
     {
         // one wave per workgroup and per SIMD (attn_bwd_dq_w1_body); option ATTN_W1 bit 1 clear: the two-wave form
@@ -1531,18 +1686,14 @@ static int launch_bwd(AttnLaunchB& bb, int np, hipStream_t s) {
         else if (biased) YT_DISPATCH(attn_bwd_dq_bias_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_fwd(dp, maxTk), s, bb);
         else YT_DISPATCH(attn_bwd_dq_kernel, dp, drop, dim3((unsigned)total), dim3(64 * nw), lds_fwd(dp, maxTk), s, b);
     }
-    // one wave per workgroup and per SIMD (attn_bwd_dkv_w1_body; option ATTN_W1 bit 2 clear: always the wave-pair form): unpadded fp32 heads, lse /
-    // delta rows staged by one wave, and at least two rounds of the 1024 wave slots (a 1.3-round launch -- 3 key tiles x 448 heads -- pays for 2:
-    // there the pair form, whose workgroups are half as long, loses less; option ATTN_W1_DKV_ANY = 1 takes the one-wave form regardless)
+    // one wave per workgroup and per SIMD (attn_bwd_dkv_w1_body) where dkv_w1_form says so.
     // Two directions in one launch: a dK/dV workgroup owns key tiles and walks the QUERY tiles, so the direction with the longer query sequence
     // has the longer workgroups; those go first (the grid is handed out in order: long ones last would leave a tail of a few hundred long
     // workgroups on a mostly idle chip -- 288-query x 80-key workgroups behind 80 x 288 ones: ~30 instead of ~24 tile times).  The forward / dQ
     // launches walk KEY tiles; BertBiAttention already passes its long-key direction first.
     if (np > 1 && b.p[1].Tq > b.p[0].Tq) swap_problems(bb);
     const int64_t w1_waves = (cdiv(b.p[0].Tk, 32) + (np > 1 ? cdiv(b.p[1].Tk, 32) : 0)) * a0.heads * a0.N;
-    const int64_t w1_slots = a0.d == 128 ? 1024 : 2048;          // (d = 64: 17 KB of LDS and < 256 registers per wave -> two per SIMD)
-    const bool w1_fill = w1_waves * 100 >= cdiv(w1_waves, w1_slots) * w1_slots * 85;      // the last round at least ~85 % useful overall
-    if (!biased && (opt(OPT_ATTN_W1) & 4) && (a0.d == 128 || a0.d == 64) && maxTq <= 512 && (w1_fill || opt(OPT_ATTN_W1_DKV_ANY))) {
+    if (!biased && dkv_w1_form(sh)) {
         b.gx0 = (int)cdiv(b.p[0].Tk, 32);
         b.gx1 = np > 1 ? (int)cdiv(b.p[1].Tk, 32) : 1;
         b.nb0 = b.gx0 * a0.heads * a0.N;
@@ -1585,13 +1736,28 @@ extern "C" int ytvln_attn_bwd_f32(const float* q, int64_t ldq, const float* k, i
                                   float* delta, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv,
                                   int N, int heads, int Tq, int Tk, int d, float scale, float p_drop, const int64_t* rng,
                                   int64_t site, void* stream) {
+    return ytvln_attn_bwd_ws_f32(q, ldq, k, ldk, v, ldv, mask, ctx, dctx, ldo, lse, delta, dq, lddq, dk, lddk, dv, lddv, N, heads, Tq, Tk, d, scale,
+                                 p_drop, rng, site, nullptr, 0, stream);
+}
+
+extern "C" int ytvln_attn_bwd_ws_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                     const float* mask, const float* ctx, const float* dctx, int64_t ldo, const float* lse,
+                                     float* delta, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv,
+                                     int N, int heads, int Tq, int Tk, int d, float scale, float p_drop, const int64_t* rng,
+                                     int64_t site, float* workspace, int64_t workspace_elems, void* stream) {
     AttnLaunchB b = {};
     AttnArgs& a = b.l.p[0];
     a.q = q; a.k = k; a.v = v; a.mask = mask; a.ctx = ctx; a.dctx = dctx; a.lse = lse; a.delta = delta;
     a.dq = dq; a.dk = dk; a.dv = dv;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
     a.N = N; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = scale; a.p_drop = p_drop; a.rng = rng; a.site = site;
-    return launch_bwd(b, 1, as_stream(stream));
+    return launch_bwd(b, 1, as_stream(stream), workspace, workspace_elems);
+}
+
+extern "C" int64_t ytvln_attn_bwd_workspace_elems(int N, int heads, int d, int Tq_a, int Tk_a, int Tq_b, int Tk_b) {
+    const bool pair = Tq_b > 0 || Tk_b > 0;
+    const BwdShape sh = {pair ? 2 : 1, N, heads, d, {Tq_a, pair ? Tq_b : 0}, {Tk_a, pair ? Tk_b : 0}};
+    return stored_ds_elems(sh);
 }
 
 // ---- both directions of BertBiAttention in one launch -----------------------------------------------------------------------
@@ -1615,11 +1781,16 @@ extern "C" int ytvln_attn_fwd_pair(const ytvln_attn_problem* pa, const ytvln_att
 
 extern "C" int ytvln_attn_bwd_pair(const ytvln_attn_problem* pa, const ytvln_attn_problem* pb, int N, int heads, int d, float scale,
                                    const int64_t* rng, void* stream) {
+    return ytvln_attn_bwd_pair_ws(pa, pb, N, heads, d, scale, rng, nullptr, 0, stream);
+}
+
+extern "C" int ytvln_attn_bwd_pair_ws(const ytvln_attn_problem* pa, const ytvln_attn_problem* pb, int N, int heads, int d, float scale,
+                                      const int64_t* rng, float* workspace, int64_t workspace_elems, void* stream) {
     YT_REQUIRE(pa && pb, "attn_bwd_pair: null problem");
     AttnLaunchB b = {};
     fill_args(b.l.p[0], *pa, N, heads, d, scale, rng);
     fill_args(b.l.p[1], *pb, N, heads, d, scale, rng);
-    return launch_bwd(b, 2, as_stream(stream));
+    return launch_bwd(b, 2, as_stream(stream), workspace, workspace_elems);
 }
 
 extern "C" int ytvln_attn_probs_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* mask, const float* lse,

@@ -32,7 +32,7 @@ int fail(int code, const char* fmt, ...);
 // use) and can be changed at run time through the C ABI; INTEGRATION.md documents every entry and tests/test_abi.py checks that its
 // table and this one agree.
 enum Option {
-    OPT_ATTN_W1 = 0,         // bit mask of the one-wave-per-SIMD attention kernels: 1 forward, 2 dQ, 4 dK/dV (default 7; 0 = two-wave forms)
+    OPT_ATTN_W1 = 0,         // bit mask of the one-wave-per-SIMD attention kernels: 1 forward, 2 dQ, 4 dK/dV, 8 stored-dS backward (default 15; 0 = two-wave forms)
     OPT_ATTN_W1_DKV_ANY,     // 1: the one-wave dK/dV kernel for launches of any size (default 0: only when its last round of wave slots is >= 85 % full)
     OPT_ATTN_DSPLIT,         // 1 (default): two-wave forward workgroups holding a single query tile split the head dimension between their waves
     OPT_GEMM_TILE,           // -1 (default): planner; 0..4 forces 128x128 / 128x64 / 64x64 / 256x128 / 256x256 where legal

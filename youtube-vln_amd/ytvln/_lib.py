@@ -66,6 +66,10 @@ SIGNATURES = {
     "ytvln_attn_dbias_bf16": [P, P, P, P, I64, I32, I32, I32, F32, P, P],
     "ytvln_attn_fwd_pair": [P, P, I32, I32, I32, F32, P, P],
     "ytvln_attn_bwd_pair": [P, P, I32, I32, I32, F32, P, P],
+    "ytvln_attn_bwd_workspace_elems": [I32, I32, I32, I32, I32, I32, I32],
+    "ytvln_attn_bwd_ws_f32": [P, I64, P, I64, P, I64, P, P, P, I64, P, P, P, I64, P, I64, P, I64, I32, I32, I32, I32, I32,
+                              F32, F32, P, I64, P, I64, P],
+    "ytvln_attn_bwd_pair_ws": [P, P, I32, I32, I32, F32, P, P, I64, P],
     "ytvln_gemm_plan": [I32, I32, I32, I32, I32, P, P, P],
     "ytvln_option_count": [],
     "ytvln_option_name": [I32],
@@ -130,7 +134,7 @@ SIGNATURES = {
     "ytvln_rccl_async_error": [P],
     "ytvln_rccl_destroy": [P],
 }
-RESTYPES = {"ytvln_attn_problem_size": I64, "ytvln_attn_dbias_workspace_elems": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
+RESTYPES = {"ytvln_attn_problem_size": I64, "ytvln_attn_bwd_workspace_elems": I64, "ytvln_attn_dbias_workspace_elems": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
 DT_F32, DT_F64, DT_BF16, DT_I64, DT_U8 = 0, 1, 2, 3, 4
 RED_SUM, RED_MAX, RED_MIN = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128

@@ -1435,9 +1435,22 @@ def _attn_launch(backward: bool, bf16: bool, pa, pb, N, heads, d, scale, rng, ba
     elif bf16:
         call("ytvln_attn_bwd_bf16" if backward else "ytvln_attn_fwd_bf16", ctypes.addressof(pa), ctypes.addressof(pb) if pb is not None else None,
              N, heads, d, float(scale), rp, _stream())
+    elif backward:
+        ws, n_ws = _attn_bwd_workspace(N, heads, d, pa.Tq, pa.Tk, pb.Tq, pb.Tk, torch.device("cuda", torch.cuda.current_device()))
+        call("ytvln_attn_bwd_pair_ws", ctypes.addressof(pa), ctypes.addressof(pb), N, heads, d, float(scale), rp, _ptr(ws), n_ws, _stream())
     else:
-        call("ytvln_attn_bwd_pair" if backward else "ytvln_attn_fwd_pair", ctypes.addressof(pa), ctypes.addressof(pb), N, heads, d, float(scale),
-             rp, _stream())
+        call("ytvln_attn_fwd_pair", ctypes.addressof(pa), ctypes.addressof(pb), N, heads, d, float(scale), rp, _stream())
+
+
+def _attn_bwd_workspace(N, heads, d, Tq_a, Tk_a, Tq_b, Tk_b, device):
+    """-> (tensor or None, floats) of the dS workspace of one fp32 backward launch (`ytvln_attn_bwd_workspace_elems`, include/ytvln.h); 0 floats when
+    the launch would not take the stored-dS form.  Allocated per call on the current stream: the caching allocator hands the block to the next
+    site once this launch's kernels, which are queued on that stream, are through with it -- safe under graph capture and with the text side on
+    its own stream."""
+    n = int(_lib.load().ytvln_attn_bwd_workspace_elems(N, heads, d, Tq_a, Tk_a, Tq_b, Tk_b))
+    if n == 0:
+        return None, 0
+    return torch.empty(n, dtype=torch.float32, device=device), n
 
 
 def _attn_fwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, N, heads, Tq, Tk, d, scale, p, rng, site, bias=None):
@@ -1469,9 +1482,10 @@ def _attn_bwd(q, q_off, ldq, k, k_off, ldk, v, v_off, ldv, mask, out, dout, lse,
                                                lse_in=lse, delta=delta, dq=dq, dq_off=dq_off, lddq=lddq, dk=dk, dk_off=dk_off, lddk=lddk,
                                                dv=dv, dv_off=dv_off, lddv=lddv, keep=keep), None, N, heads, d, scale, rng, ba=brec)
         return delta
-    call("ytvln_attn_bwd_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(v, v_off), ldv, _ptr(mask), _ptr(out), _ptr(dout),
+    ws, n_ws = _attn_bwd_workspace(N, heads, d, Tq, Tk, 0, 0, q.device)
+    call("ytvln_attn_bwd_ws_f32", _ptr(q, q_off), ldq, _ptr(k, k_off), ldk, _ptr(v, v_off), ldv, _ptr(mask), _ptr(out), _ptr(dout),
          out.shape[-1], _ptr(lse), _ptr(delta), _ptr(dq, dq_off), lddq, _ptr(dk, dk_off), lddk, _ptr(dv, dv_off), lddv, N, heads, Tq,
-         Tk, d, float(scale), float(p), _ptr(rng) if rng is not None else None, int(site), _stream())
+         Tk, d, float(scale), float(p), _ptr(rng) if rng is not None else None, int(site), _ptr(ws), n_ws, _stream())
     return delta
 
 
