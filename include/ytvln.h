@@ -497,6 +497,43 @@ int ytvln_ema_update(const float* p, float* e, const void* chunks, int nchunks, 
  * parameter, 18 with the copy. */
 int ytvln_ema_swap(float* p, float* e, uint16_t* p_bf16, const void* chunks, int nchunks, void* stream);
 
+/* ---- heads of the downstream-task model (VILBertForVLTasks / SimpleClassifier, vilbert.py:1457-1535) -------------------------------------
+ * None of these uses an atomic: every reduction runs in an order fixed by the shapes alone, so two launches on the same inputs give the
+ * same bits.
+ *
+ * Weight normalisation with dim = None (vilbert.py:1522-1535: weight_norm(nn.Linear(...), dim=None)): w = v g / |v|_F with ONE scalar g (a
+ * device pointer) per matrix of n elements.  Forward: stat[0] = |v|_2 over all n elements, stat[1] = g / stat[0], w[i] = v[i] stat[1], and
+ * w_bf16[i] (when not NULL, 8-byte aligned) the round-to-nearest-even copy of w[i].  |v| = 0 is not special-cased (the reference yields
+ * non-finite values there too).  Backward, from dw = dL/dw and the forward's stat: dg = <dw, v> / |v|, dv = s dw - (s <dw, v> / |v|^2) v with
+ * s = stat[1]; dv and dg are plain stores (they may point into gradient-arena slots).  The sums run in two stages -- fixed contiguous chunks
+ * per workgroup, then the partials in index order -- through `workspace` of ytvln_weight_norm_workspace_elems(n) floats, which is scratch
+ * inside the call.  v, w, dw, dv 16-byte aligned; any n > 0. */
+int64_t ytvln_weight_norm_workspace_elems(int64_t n);
+int ytvln_weight_norm_fwd_f32(const float* v, const float* g, int64_t n, float* w, uint16_t* w_bf16, float* stat, float* workspace, void* stream);
+int ytvln_weight_norm_bwd_f32(const float* v, const float* dw, const float* stat, int64_t n, float* dv, float* dg, float* workspace, void* stream);
+
+/* A Linear with ONE output feature over every row, with the dropout in front of it and the additive region mask behind it
+ * (vilbert.py:1517-1518: vision_logit = Linear(v_hidden, 1)(dropout(sequence_output_v)) + (1 - image_attention_mask) * -10000, and
+ * linguisic_logit likewise without the mask term):
+ *   out[r] = (sum_c k(r,c) x[r,c] w[c] + bias) + (1 - mask[r]) * -10000
+ * x is [rows, H] with leading dimension ldx, fp32 or bf16; w is fp32 [H]; bias fp32 [1] or NULL; mask fp32 [rows] of 0 / 1 or NULL; out is
+ * fp32 [rows].  k(r,c) is the keep-scale ytvln_dropout_f32 applies at flat element r * H + c of the same (rng, site) -- independent of ldx --
+ * and 1 when p == 0 (rng may then be NULL).  One wave per row, 16 bytes per lane, fp32 accumulation.
+ * Backward, in one pass over x: dx[r,c] = k(r,c) dy[r] w[c] in x's type (dx may be NULL), dw[c] = sum_r dy[r] k(r,c) x[r,c], db = sum_r dy[r]
+ * (db may be NULL); the mask gets no gradient.  The row sums go through `workspace` of ytvln_row_logit_workspace_elems(rows, H) floats: each
+ * workgroup owns a contiguous run of rows and writes one partial row, a second kernel adds the partial rows in run order.
+ * H % 4 == 0 (fp32) or H % 8 == 0 (bf16), H <= 2048; ldx / lddx multiples of the same granule; x, w, dx, dw, workspace 16-byte aligned;
+ * 0 <= p < 1. */
+int64_t ytvln_row_logit_workspace_elems(int64_t rows, int H);
+int ytvln_row_logit_fwd_f32(const float* x, int64_t ldx, const float* w, const float* bias, const float* mask, float* out, int64_t rows, int H,
+                            float p, const int64_t* rng, int64_t site, void* stream);
+int ytvln_row_logit_fwd_bf16(const uint16_t* x, int64_t ldx, const float* w, const float* bias, const float* mask, float* out, int64_t rows, int H,
+                             float p, const int64_t* rng, int64_t site, void* stream);
+int ytvln_row_logit_bwd_f32(const float* x, int64_t ldx, const float* w, const float* dy, int64_t rows, int H, float p, const int64_t* rng,
+                            int64_t site, float* dx, int64_t lddx, float* dw, float* db, float* workspace, void* stream);
+int ytvln_row_logit_bwd_bf16(const uint16_t* x, int64_t ldx, const float* w, const float* dy, int64_t rows, int H, float p, const int64_t* rng,
+                             int64_t site, uint16_t* dx, int64_t lddx, float* dw, float* db, float* workspace, void* stream);
+
 /* ---- data-parallel gradient exchange: RCCL over xGMI ------------------------------------------------------------------------
  * Replaces DistributedDataParallel over NCCL (utils/distributed.py:63-104: init_process_group("nccl") + DDP's bucketed all-reduce).
  * librccl is resolved with dlopen at run time (no link dependency): an explicit path, else a librccl already mapped into the

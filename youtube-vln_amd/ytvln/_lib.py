@@ -100,6 +100,15 @@ SIGNATURES = {
     "ytvln_lamb_stage2": [P, P, P, P, P, I32, P, P, P, P, P],
     "ytvln_ema_update": [P, P, P, I32, P, P, P],
     "ytvln_ema_swap": [P, P, P, P, I32, P],
+    # heads of VILBertForVLTasks (csrc/heads.hip)
+    "ytvln_weight_norm_workspace_elems": [I64],
+    "ytvln_weight_norm_fwd_f32": [P, P, I64, P, P, P, P, P],
+    "ytvln_weight_norm_bwd_f32": [P, P, P, I64, P, P, P, P],
+    "ytvln_row_logit_workspace_elems": [I64, I32],
+    "ytvln_row_logit_fwd_f32": [P, I64, P, P, P, P, I64, I32, F32, P, I64, P],
+    "ytvln_row_logit_fwd_bf16": [P, I64, P, P, P, P, I64, I32, F32, P, I64, P],
+    "ytvln_row_logit_bwd_f32": [P, I64, P, P, I64, I32, F32, P, I64, P, I64, P, P, P, P],
+    "ytvln_row_logit_bwd_bf16": [P, I64, P, P, I64, I32, F32, P, I64, P, I64, P, P, P, P],
     "ytvln_ln_fwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, I64, P],
     "ytvln_ln_bwd_blocks": [I64],
     "ytvln_ln_bwd_f32": [P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],
@@ -134,7 +143,7 @@ SIGNATURES = {
     "ytvln_rccl_async_error": [P],
     "ytvln_rccl_destroy": [P],
 }
-RESTYPES = {"ytvln_attn_problem_size": I64, "ytvln_attn_bwd_workspace_elems": I64, "ytvln_attn_dbias_workspace_elems": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
+RESTYPES = {"ytvln_weight_norm_workspace_elems": I64, "ytvln_row_logit_workspace_elems": I64, "ytvln_attn_problem_size": I64, "ytvln_attn_bwd_workspace_elems": I64, "ytvln_attn_dbias_workspace_elems": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
 DT_F32, DT_F64, DT_BF16, DT_I64, DT_U8 = 0, 1, 2, 3, 4
 RED_SUM, RED_MAX, RED_MIN = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128

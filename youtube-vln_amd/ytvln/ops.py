@@ -1365,6 +1365,121 @@ def dropout(x: Tensor, p: float, training: bool, drop: Optional[DropoutState]) -
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# heads of the downstream-task model (vilbert.py:1457-1535): weight normalisation over a whole matrix, one-feature Linear over rows
+# ------------------------------------------------------------------------------------------------------------------
+class WeightNormFn(torch.autograd.Function):
+    """w = v * g / ||v||_F with one scalar g per matrix (torch.nn.utils.weight_norm(..., dim=None), vilbert.py:1526-1529).  The backward takes
+    dL/dw from the projection that consumed w and writes dv / dg straight into the gradient arena when the two parameters live there."""
+
+    @staticmethod
+    def forward(ctx, v, g):
+        ctx.set_materialize_grads(False)
+        _check(v, "weight_v")
+        _check(g, "weight_g")
+        if g.numel() != 1:
+            raise RuntimeError(f"ytvln.ops.weight_norm: weight_g must hold one element (dim=None); got shape {tuple(g.shape)}")
+        vc = v if v.is_contiguous() else v.contiguous()
+        n = vc.numel()
+        w = torch.empty_like(vc)
+        stat = torch.empty(2, dtype=torch.float32, device=v.device)
+        ws = torch.empty(_lib.load().ytvln_weight_norm_workspace_elems(n), dtype=torch.float32, device=v.device)
+        # no bf16 copy of w (the kernel can write one): the only consumer, SimpleClassifier, feeds the fp32 GEMM in every precision mode
+        call("ytvln_weight_norm_fwd_f32", _ptr(vc), _ptr(g), n, _ptr(w), None, _ptr(stat), _ptr(ws), _stream())
+        ctx.vtargets, ctx.gtargets = _targets_of(v), _targets_of(g)
+        ctx.save_for_backward(vc, stat)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        if dw is None:
+            return None, None
+        vc, stat = ctx.saved_tensors
+        dwc = dw if dw.is_contiguous() else dw.contiguous()
+        n = vc.numel()
+        dv = _direct_grad(ctx.vtargets, vc.shape)
+        if dv is None:
+            dv = torch.empty_like(vc)
+        dg = _direct_grad(ctx.gtargets, ())
+        if dg is None:
+            dg = torch.empty((), dtype=torch.float32, device=vc.device)
+        ws = torch.empty(_lib.load().ytvln_weight_norm_workspace_elems(n), dtype=torch.float32, device=vc.device)
+        call("ytvln_weight_norm_bwd_f32", _ptr(vc), _ptr(dwc), _ptr(stat), n, _ptr(dv), _ptr(dg), _ptr(ws), _stream())
+        return dv, dg
+
+
+def weight_norm(v: Tensor, g: Tensor) -> Tensor:
+    """The effective weight of a weight-normed Linear: pass it to `linear` like any [out, in] weight."""
+    return WeightNormFn.apply(v, g)
+
+
+class RowLogitFn(torch.autograd.Function):
+    """out[..., 0] = (dropout(x) . w + b) + (1 - mask) * -10000: nn.Linear(H, 1) over every row of an fp32 or bf16 hidden state, fused with the
+    dropout in front of it and the region-mask term behind it (vilbert.py:1517-1518).  The output is fp32; dx has x's type."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mask, p, rng, site):
+        ctx.set_materialize_grads(False)
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f"ytvln.ops.row_logit: `x` must be float32 or bfloat16; got {x.dtype}")
+        x2, rows, H, ldx = _rows2d_any(x)
+        _check(weight, "weight")
+        if weight.numel() != H:
+            raise RuntimeError(f"ytvln.ops.row_logit: weight of {weight.numel()} elements for rows of {H}")
+        ctx.wtargets, ctx.btargets = _targets_of(weight), (_targets_of(bias) if bias is not None else None)
+        weight = weight if weight.is_contiguous() else weight.contiguous()
+        if bias is not None:
+            _check(bias, "bias")
+        if mask is not None:
+            if mask.numel() != rows:
+                raise RuntimeError(f"ytvln.ops.row_logit: mask of {mask.numel()} elements for {rows} rows")
+            if mask.dtype != torch.float32 or not mask.is_contiguous():          # (an integer mask: one small cast; an fp32 one is read in place)
+                mask = mask.to(torch.float32).contiguous()
+            _check(mask, "mask")
+        ctx.kind = "bf16" if x.dtype == torch.bfloat16 else "f32"
+        out = torch.empty(rows, dtype=torch.float32, device=x.device)
+        call("ytvln_row_logit_fwd_" + ctx.kind, x2.data_ptr(), ldx, _ptr(weight), _ptr(bias), _ptr(mask), _ptr(out), rows, H, float(p),
+             _ptr(rng), int(site), _stream())
+        ctx.dims, ctx.p, ctx.site, ctx.in_shape = (rows, H, ldx), float(p), int(site), x.shape
+        ctx.wshape, ctx.has_bias = weight.shape, bias is not None
+        ctx.save_for_backward(x2, weight, rng)
+        return out.view(tuple(x.shape[:-1]) + (1,))
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 7
+        x2, weight, rng = ctx.saved_tensors
+        rows, H, ldx = ctx.dims
+        dyc = dy.reshape(rows)
+        if dyc.dtype != torch.float32 or not dyc.is_contiguous():
+            dyc = dyc.to(torch.float32).contiguous()
+        dx = torch.empty((rows, H), dtype=x2.dtype, device=x2.device) if ctx.needs_input_grad[0] else None
+        dw = _direct_grad(ctx.wtargets, ctx.wshape)
+        if dw is None:
+            dw = torch.empty(ctx.wshape, dtype=torch.float32, device=x2.device)
+        db = None
+        if ctx.has_bias:
+            db = _direct_grad(ctx.btargets, (1,))
+            if db is None:
+                db = torch.empty(1, dtype=torch.float32, device=x2.device)
+        ws = torch.empty(_lib.load().ytvln_row_logit_workspace_elems(rows, H), dtype=torch.float32, device=x2.device)
+        call("ytvln_row_logit_bwd_" + ctx.kind, x2.data_ptr(), ldx, _ptr(weight), _ptr(dyc), rows, H, ctx.p, _ptr(rng), ctx.site,
+             dx.data_ptr() if dx is not None else None, H, _ptr(dw), _ptr(db), _ptr(ws), _stream())
+        return (dx.view(ctx.in_shape) if dx is not None else None), dw, db, None, None, None, None
+
+
+def row_logit(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, mask: Optional[Tensor] = None, p: float = 0.0, training: bool = False,
+              drop: Optional[DropoutState] = None) -> Tensor:
+    """[..., H] -> [..., 1] fp32.  `mask` ([...] of 0 / 1, optional) adds (1 - mask) * -10000; dropout with probability p in training mode takes
+    its site from `drop` like `dropout`."""
+    if training and p > 0.0:
+        if drop is None:
+            raise RuntimeError("dropout requested without a DropoutState")
+        return RowLogitFn.apply(x, weight, bias, mask, p, drop.tensor, drop.next_site())
+    return RowLogitFn.apply(x, weight, bias, mask, 0.0, None, 0)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------------------------
 def _eptr(t: Optional[Tensor], offset_elems: int = 0):

@@ -25,6 +25,7 @@ import json
 import logging
 import math
 import os
+import warnings
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -940,3 +941,68 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
             next_sentence_loss = ops.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.view(-1), -1)
             return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
         return prediction_scores_t, prediction_scores_v, seq_relationship_score, all_attention_mask
+
+
+class SimpleClassifier(nn.Module):
+    """vilbert.py:1522-1535: Linear -> ReLU -> Dropout -> Linear, both projections weight-normed over the whole matrix (dim=None: `weight_g` is
+    0-d).  The two containers are registered through torch's own weight_norm so that construction consumes the reference's generator draws
+    and the state-dict keys are `main.{0,3}.{bias,weight_g,weight_v}`; the wrapped Linear is never called -- the effective weight comes from
+    ops.weight_norm and feeds the fp32 GEMM in every precision mode (the pooled vectors are fp32, and a weight that is recomputed every
+    forward has no bf16 copy in the optimizer's arena to read)."""
+
+    def __init__(self, in_dim, hid_dim, out_dim, dropout):
+        super().__init__()
+        with warnings.catch_warnings():          # (the hook-based weight_norm is deprecated in torch, and is what names the keys weight_g / weight_v)
+            warnings.simplefilter("ignore", FutureWarning)
+            first = torch.nn.utils.weight_norm(nn.Linear(in_dim, hid_dim), dim=None)
+            last = torch.nn.utils.weight_norm(nn.Linear(hid_dim, out_dim), dim=None)
+        self.main = nn.Sequential(first, nn.ReLU(), nn.Dropout(dropout, inplace=True), last)
+
+    def forward(self, x):
+        first, drop, last = self.main[0], self.main[2], self.main[3]
+        h = ops.LinearFn.apply(x, ops.weight_norm(first.weight_v, first.weight_g), first.bias, "relu")
+        h = ops.dropout(h, drop.p, self.training, _drop_state(self, h))
+        return ops.LinearFn.apply(h, ops.weight_norm(last.weight_v, last.weight_g), last.bias, None)
+
+
+class VILBertForVLTasks(BertPreTrainedModel):
+    """vilbert.py:1457-1520: the downstream-task model.  Returns (vil_prediction [N, num_labels], vil_logit [N, 1], vil_binary_prediction [N, 2],
+    vision_prediction [N, R, v_target], vision_logit [N, R, 1], linguisic_prediction [N, T, vocab], linguisic_logit [N, T, 1]).  The two
+    per-row logits run on ops.row_logit (dropout, dot product and region-mask term in one kernel, fp32 out on fp32 or bf16 hidden states)."""
+
+    def __init__(self, config, num_labels, dropout_prob=0.1, default_gpu=True):
+        super().__init__(config)
+        self.num_labels = num_labels
+        self.bert = BertModel(config)
+        self.dropout = nn.Dropout(dropout_prob)
+        self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight)
+        self.vil_prediction = SimpleClassifier(config.bi_hidden_size, config.bi_hidden_size * 2, num_labels, 0.5)
+        self.vil_logit = nn.Linear(config.bi_hidden_size, 1)
+        self.vision_logit = nn.Linear(config.v_hidden_size, 1)
+        self.linguisic_logit = nn.Linear(config.hidden_size, 1)
+        self.fusion_method = config.fusion_method
+        self.apply(self.init_bert_weights)
+
+    def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
+                co_attention_mask=None, output_all_encoded_layers=False):
+        sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, _ = self.bert(
+            input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask, co_attention_mask,
+            output_all_encoded_layers=False)
+        linguisic_prediction, vision_prediction, vil_binary_prediction = self.cls(
+            sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v)
+        if self.fusion_method == "sum":
+            pooled_output = pooled_output_t + pooled_output_v
+        elif self.fusion_method == "mul":
+            pooled_output = pooled_output_t * pooled_output_v
+        else:
+            assert False
+        p = self.dropout.p
+        pooled_output = ops.dropout(pooled_output, p, self.training, _drop_state(self, pooled_output))
+        vil_prediction = self.vil_prediction(pooled_output)
+        vil_logit = ops.linear(pooled_output, self.vil_logit.weight, self.vil_logit.bias)
+        # (the reference has no branch for a missing region mask: it fails on `1.0 - None`; here that means "every region attended")
+        vision_logit = ops.row_logit(sequence_output_v, self.vision_logit.weight, self.vision_logit.bias, image_attention_mask, p,
+                                     self.training, _drop_state(self, sequence_output_v))
+        linguisic_logit = ops.row_logit(sequence_output_t, self.linguisic_logit.weight, self.linguisic_logit.bias, None, p,
+                                        self.training, _drop_state(self, sequence_output_t))
+        return (vil_prediction, vil_logit, vil_binary_prediction, vision_prediction, vision_logit, linguisic_prediction, linguisic_logit)
