@@ -534,6 +534,24 @@ int ytvln_row_logit_bwd_f32(const float* x, int64_t ldx, const float* w, const f
 int ytvln_row_logit_bwd_bf16(const uint16_t* x, int64_t ldx, const float* w, const float* dy, int64_t rows, int H, float p, const int64_t* rng,
                              int64_t site, uint16_t* dx, int64_t lddx, float* dw, float* db, float* workspace, void* stream);
 
+/* ---- losses of the downstream tasks (VQA-style answer classification over vil_prediction, grounding over vision_logit) ------------------
+ * Row-wise soft-target BCE with logits over a matrix x[M, C] (fp32, leading dimension ldx) and targets t[M, C] (fp32, ldt), any M * C:
+ *   term(r,c) = (1 - t) x + (1 + (w(c) - 1) t) log(1 + exp(-x))        the term of ytvln_bce_fwd_f32
+ *   w(c) = pos_weight[c * pw_stride];  pos_weight NULL: w = 1;  pw_stride 0: one DEVICE scalar, 1: one weight per class (torch's pos_weight)
+ *   loss = scale * sum(term) / (M C)                                    scale = C: the sum over classes, averaged over the rows
+ * fwd, two launches: one workgroup per row streams x and t once and writes row_loss[r], row_top[r] = the LOWEST index of the row's maximum
+ * logit (torch.argmax's tie rule) and row_hit[r] = t[r, row_top[r]]; a single workgroup then writes out[0] = float(sum(row_loss) * scale /
+ * (M C)) and out[1] = sum(row_hit), both sums in fp64.  A row holding a NaN logit makes the loss NaN; its row_top / row_hit are unspecified
+ * (in bounds).  bwd, one launch: dx[r,c] = ((1 - t) - (1 + (w(c) - 1) t) / (1 + exp(x))) * gout[0] * scale / (M C) into columns [0, C) of dx
+ * (leading dimension lddx; padding columns are not written); t and pos_weight get no gradient.
+ * No atomics, every summation order fixed by the shapes alone: two launches on the same inputs give the same bits.  fp32 only (both
+ * producers, SimpleClassifier and ytvln_row_logit_fwd_*, write fp32 in every precision mode).  Plain 4-byte loads and stores: every float
+ * pointer 4-byte aligned, row_top 8-byte aligned, any ldx, ldt, lddx >= C.  scale must be finite. */
+int ytvln_bce_rows_fwd_f32(const float* x, int64_t ldx, const float* t, int64_t ldt, const float* pos_weight, int pw_stride, float scale,
+                           float* row_loss, float* row_hit, int64_t* row_top, float* out, int M, int C, void* stream);
+int ytvln_bce_rows_bwd_f32(const float* x, int64_t ldx, const float* t, int64_t ldt, const float* pos_weight, int pw_stride, float scale,
+                           const float* gout, float* dx, int64_t lddx, int M, int C, void* stream);
+
 /* ---- data-parallel gradient exchange: RCCL over xGMI ------------------------------------------------------------------------
  * Replaces DistributedDataParallel over NCCL (utils/distributed.py:63-104: init_process_group("nccl") + DDP's bucketed all-reduce).
  * librccl is resolved with dlopen at run time (no link dependency): an explicit path, else a librccl already mapped into the

@@ -127,6 +127,9 @@ SIGNATURES = {
     "ytvln_kl_bwd_f32": [P, I64, P, I64, P, P, P, P, P, I64, I32, I32, P],
     "ytvln_bce_fwd_f32": [P, P, P, P, I32, P],
     "ytvln_bce_bwd_f32": [P, P, P, P, P, I32, P],
+    # losses of the downstream tasks (csrc/task_loss.hip)
+    "ytvln_bce_rows_fwd_f32": [P, I64, P, I64, P, I32, F32, P, P, P, P, I32, I32, P],
+    "ytvln_bce_rows_bwd_f32": [P, I64, P, I64, P, I32, F32, P, P, I64, I32, I32, P],
     "ytvln_adamw_f32": [P, P, P, P, P, I32, P, F32, P],
     # RCCL binding (csrc/rccl.hip): host calls, the communicator is an opaque handle
     "ytvln_rccl_load": [P],

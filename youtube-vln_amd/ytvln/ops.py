@@ -1906,6 +1906,59 @@ def bce_with_logits(x: Tensor, t: Tensor, pos_weight: Optional[Tensor] = None) -
     return BCEWithLogitsFn.apply(x, t, pos_weight)
 
 
+class BCERowsFn(torch.autograd.Function):
+    """scale * mean(bce_with_logits(x, t, pos_weight)) over a [M, C] matrix of any size, with the row arg-max and the sum of the targets at it
+    (the score of a soft-target classification task) from the same pass.  fp32 logits only: both producers of such logits write fp32."""
+
+    @staticmethod
+    def forward(ctx, x, t, pos_weight, scale):
+        ctx.set_materialize_grads(False)
+        x2, M, Cc, ldx = _rows2d(x, "x")
+        if not t.is_cuda:
+            raise RuntimeError(f"ytvln.ops: `t` must live on the GPU (no CPU fallback); got device {t.device}")
+        t2, M2, C2, ldt = _rows2d(t if t.dtype == torch.float32 else t.to(torch.float32), "t")
+        if (M, Cc) != (M2, C2):
+            raise RuntimeError(f"ytvln.ops.bce_with_logits_rows: logits {tuple(x.shape)} against targets {tuple(t.shape)}")
+        pw, pw_stride = None, 0
+        if pos_weight is not None:
+            if pos_weight.numel() not in (1, Cc):
+                raise RuntimeError(f"ytvln.ops.bce_with_logits_rows: pos_weight of {pos_weight.numel()} elements for {Cc} classes")
+            pw = pos_weight.to(torch.float32).reshape(-1).contiguous()
+            _check(pw, "pos_weight")
+            pw_stride = 1 if pw.numel() == Cc and Cc > 1 else 0
+        dev = x2.device
+        row_loss = torch.empty(M, dtype=torch.float32, device=dev)
+        row_hit = torch.empty(M, dtype=torch.float32, device=dev)
+        row_top = torch.empty(M, dtype=torch.int64, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        call("ytvln_bce_rows_fwd_f32", _ptr(x2), ldx, _ptr(t2), ldt, _ptr(pw), pw_stride, float(scale), _ptr(row_loss), _ptr(row_hit),
+             row_top.data_ptr(), _ptr(out), M, Cc, _stream())
+        ctx.meta = (M, Cc, ldx, ldt, pw_stride, float(scale), x.shape)
+        ctx.save_for_backward(x2, t2, pw)
+        loss, score = out[0], out[1]
+        ctx.mark_non_differentiable(score, row_top)
+        return loss, score, row_top
+
+    @staticmethod
+    def backward(ctx, g, _gscore=None, _gtop=None):
+        if g is None:
+            return None, None, None, None
+        x2, t2, pw = ctx.saved_tensors
+        M, Cc, ldx, ldt, pw_stride, scale, shape = ctx.meta
+        g = g.reshape(1).contiguous().float()
+        dx, lddx = _alloc_rows(M, Cc, x2.device, zero_pad=True)
+        call("ytvln_bce_rows_bwd_f32", _ptr(x2), ldx, _ptr(t2), ldt, _ptr(pw), pw_stride, scale, _ptr(g), _ptr(dx), lddx, M, Cc, _stream())
+        return _view_rows_as(dx, lddx, shape), None, None, None
+
+
+def bce_with_logits_rows(x: Tensor, t: Tensor, pos_weight: Optional[Tensor] = None, scale: float = 1.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """(loss, score, row_top) of a [..., C] logit matrix of any size against soft targets of the same shape:
+    loss = scale * F.binary_cross_entropy_with_logits(x, t, pos_weight=pos_weight) (0-d, differentiable in x), row_top[r] = argmax of row r
+    (int64, lowest index among equals), score = sum_r t[r, row_top[r]] (0-d).  `pos_weight`: None, one element, or [C].  A padded LinearFn
+    output is read through its leading dimension, without a copy."""
+    return BCERowsFn.apply(x, t, pos_weight, scale)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # optimizer kernel
 # ------------------------------------------------------------------------------------------------------------------
