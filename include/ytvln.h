@@ -232,6 +232,13 @@ int ytvln_act_bwd_f32(const float* dy, const float* aux, float* dz, int64_t n, i
  * (sigmoid is formed from exp(-|z|) <= 1).  Other values of act are rejected: gelu / relu stay GEMM epilogues. */
 int ytvln_act_fwd_f32(const float* z, float* y, int64_t n, int act, void* stream);
 
+/* h = gelu(z) elementwise, z the pre-activation an YTVLN_EPI_GELU launch of ytvln_gemm_f32 wrote to `aux`: the same device function as that
+ * epilogue, so h is the epilogue's output bit for bit (activation recomputation, recompute = "ffn": the FFN node keeps z and rebuilds h in its
+ * backward).  Any n >= 0 (n = 0 succeeds with NULL pointers), any alignment, h == z allowed; 16 bytes per lane when both pointers are 16-byte
+ * aligned, one element per lane otherwise; nothing is written at or past n.  fp32 only: on the bf16-resident path z is stored rounded, and
+ * gelu of the rounded z is not the stored h. */
+int ytvln_gelu_fwd_f32(const float* z, float* h, int64_t n, void* stream);
+
 /* y = x * keep / (1 - p): nn.Dropout forward and (applied to dy) backward (lily.py:100). */
 int ytvln_dropout_f32(const float* x, float* y, int64_t n, float p, const int64_t* rng, int64_t site, void* stream);
 

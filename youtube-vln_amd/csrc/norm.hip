@@ -667,6 +667,29 @@ __global__ __launch_bounds__(256) void swish_fwd_kernel(const float* z, float* y
     }
 }
 
+// h = gelu_erf(z): the output of the fp32 GEMM's EPI_GELU epilogue, recomputed from the pre-activation that epilogue wrote to `aux` -- the same
+// device function on the same fp32 value, hence the same bits (FFNFn with recompute = "ffn" keeps z only and calls this just before the dW2
+// GEMM of its backward).  A pure streaming pass, shaped like swish_fwd_kernel: VEC = 16 bytes per lane over the first n & ~3 elements and block 0
+// finishes the tail one element per lane; !VEC (a pointer off the 16-byte grid) = one element per lane throughout.  Nothing is written at or
+// past n.  h == z is allowed (every lane reads exactly what it writes).
+template <bool VEC>
+__global__ __launch_bounds__(256) void gelu_fwd_kernel(const float* z, float* h, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += step) {
+            const float4 v = ld4(z, i);
+            st4(h, i, make_float4(gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w)));
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+            const int64_t i = (n4 << 2) + threadIdx.x;
+            h[i] = gelu_erf(z[i]);
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += step) h[i] = gelu_erf(z[i]);
+    }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void swish_fwd_bf16_kernel(const bf16_t* z, bf16_t* y, int64_t n) {
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
@@ -950,6 +973,18 @@ extern "C" int ytvln_act_fwd_f32(const float* z, float* y, int64_t n, int act, v
     else
         hipLaunchKernelGGL(swish_fwd_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), z, y, n);
     YT_LAUNCH_CHECK("act_fwd");
+    return 0;
+}
+
+extern "C" int ytvln_gelu_fwd_f32(const float* z, float* h, int64_t n, void* stream) {
+    YT_REQUIRE(n >= 0, "gelu_fwd: n < 0");
+    if (n == 0) return 0;          // (an empty tensor has no address)
+    YT_REQUIRE(z && h, "gelu_fwd: null pointer");
+    if (al16(z) && al16(h))
+        hipLaunchKernelGGL(gelu_fwd_kernel<true>, dim3(ew_grid(n / 4)), dim3(256), 0, as_stream(stream), z, h, n);
+    else
+        hipLaunchKernelGGL(gelu_fwd_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), z, h, n);
+    YT_LAUNCH_CHECK("gelu_fwd");
     return 0;
 }
 

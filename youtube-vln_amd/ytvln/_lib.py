@@ -116,6 +116,7 @@ SIGNATURES = {
     "ytvln_image_embed_fwd_f32": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, I64, P],
     "ytvln_act_bwd_f32": [P, P, P, I64, I32, P],
     "ytvln_act_fwd_f32": [P, P, I64, I32, P],
+    "ytvln_gelu_fwd_f32": [P, P, I64, P],
     "ytvln_dropout_f32": [P, P, I64, F32, P, I64, P],
     "ytvln_attn_fwd_f32": [P, I64, P, I64, P, I64, P, P, I64, P, I32, I32, I32, I32, I32, F32, F32, P, I64, P],
     "ytvln_attn_bwd_f32": [P, I64, P, I64, P, I64, P, P, P, I64, P, P, P, I64, P, I64, P, I64, I32, I32, I32, I32, I32,

@@ -567,6 +567,11 @@ class GraphedTrainStep:
     def __init__(self, model: nn.Module, optimizer, fwd_bwd: Callable[[], torch.Tensor], bucket_bytes: int = 256 << 20, group=None,
                  mode: Optional[str] = None):
         self.opt, self.group, self.bucket_bytes = optimizer, group, bucket_bytes
+        for m in model.modules():          # activation recomputation re-enters autograd from inside the backward pass: not captured, in any mode
+            tier = getattr(m, "recompute", "none") if hasattr(m, "cut_after") else "none"
+            if tier != "none":
+                raise NotImplementedError(f"GraphedTrainStep with BertEncoder.recompute = {tier!r}: a recomputing backward is not captured into "
+                                          'hipGraphs; set encoder.recompute = "none" for graph-replayed steps (eager train_step takes every tier)')
         dp = model if isinstance(model, DataParallel) else None
         self.comm = dp.comm if dp is not None else None
         self.world = dp.world if dp is not None else (dist.get_world_size(group) if dist.is_initialized() else 1)

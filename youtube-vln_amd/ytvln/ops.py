@@ -680,12 +680,17 @@ def linear_res(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, act: Op
 
 class FFNFn(torch.autograd.Function):
     """out = gelu(x W1^T + b1) W2^T + b2   (BertIntermediate + BertOutput.dense, vilbert.py:351-354, 365).
-    Backward fuses the GELU derivative into the epilogue of the dX GEMM of the second projection."""
+    Backward fuses the GELU derivative into the epilogue of the dX GEMM of the second projection.
+
+    `recompute_h=True` (BertEncoder.recompute = "ffn"): the node keeps the pre-activation z and not h = gelu(z) -- M x I x 4 bytes less per FFN
+    between forward and backward -- and its backward rebuilds h with ytvln_gelu_fwd_f32 (the epilogue's own device function on the stored z:
+    the same bits) into a buffer that lives from just before the dW2 GEMM to just after it.  Everything else is the default path."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, passthrough=False):
+    def forward(ctx, x, w1, b1, w2, b2, passthrough=False, recompute_h=False):
         ctx.set_materialize_grads(False)
         ctx.passthrough = bool(passthrough)
+        ctx.recompute_h = bool(recompute_h)
         x2, M, K, lda = _rows2d(x, "x")
         I, N = w1.shape[0], w2.shape[0]
         need_grad = any(ctx.needs_input_grad)
@@ -696,14 +701,15 @@ class FFNFn(torch.autograd.Function):
         _gemm(h, I, 0, w2, w2.stride(0), 1, y, N, M, N, I, bias=b2)
         ctx.dims, ctx.lda, ctx.in_shape = (M, K, I, N), lda, x.shape
         ctx.targets = (_targets_of(w1), _targets_of(w2), _targets_of(b1), _targets_of(b2))
-        ctx.save_for_backward(x2, w1, w2, z, h)
+        ctx.save_for_backward(x2, w1, w2, z, None if ctx.recompute_h else h)
         out = y.view(*x.shape[:-1], N)
         return (out, x) if ctx.passthrough else out
 
     @staticmethod
     def backward(ctx, dy, dres=None):
+        tail = (None,) * (len(ctx.needs_input_grad) - 5)          # passthrough / recompute_h: as many as the call passed
         if dy is None:
-            return (dres if ctx.needs_input_grad[0] else None), None, None, None, None, None
+            return ((dres if ctx.needs_input_grad[0] else None), None, None, None, None) + tail
         x2, w1, w2, z, h = ctx.saved_tensors
         M, K, I, N = ctx.dims
         dy = dy.reshape(M, N)
@@ -721,7 +727,12 @@ class FFNFn(torch.autograd.Function):
         dw2 = _direct_grad(ctx.targets[1], (N, I))
         if dw2 is None:
             dw2 = torch.empty((N, I), dtype=torch.float32, device=dev)
-        if not _gemm(dy, N, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2):          # db2 rides on the dW2 GEMM
+        if h is None:          # recompute_h: h = gelu(z), alive for the one GEMM that reads it
+            h = torch.empty((M, I), dtype=torch.float32, device=dev)
+            call("ytvln_gelu_fwd_f32", _ptr(z), _ptr(h), M * I, _stream())
+        db2_done = _gemm(dy, N, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2)          # db2 rides on the dW2 GEMM
+        del h
+        if not db2_done:
             colsum(dy, M, N, N, out=db2)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -740,19 +751,33 @@ class FFNFn(torch.autograd.Function):
             dw1 = torch.empty((I, K), dtype=torch.float32, device=dev)
         if not _gemm(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1):
             colsum(dz, M, I, I, out=db1)
-        return dx, dw1, db1, dw2, db2, None
+        return (dx, dw1, db1, dw2, db2) + tail
 
 
-def ffn(x, w1, b1, w2, b2) -> Tensor:
+_NO_BF16_RECOMPUTE_H = ('recompute = "ffn" with bf16 hidden states: the bf16-resident path stores the GELU pre-activation z rounded to bf16, and '
+                        'bf16(gelu(float(bf16 z))) is not the stored h -- the tier would not be exact.  Use recompute = "layer" (exact on this '
+                        'path) or "none"')
+
+
+def ffn(x, w1, b1, w2, b2, recompute_h: bool = False) -> Tensor:
+    """`recompute_h`: see FFNFn (fp32 hidden states only; bf16 ones are refused)."""
     if x.dtype == torch.bfloat16:
+        if recompute_h:
+            raise NotImplementedError(_NO_BF16_RECOMPUTE_H)
         return FFNBf16Fn.apply(x, w1, b1, w2, b2)
+    if recompute_h:
+        return FFNFn.apply(x, w1, b1, w2, b2, False, True)
     return FFNFn.apply(x, w1, b1, w2, b2)
 
 
-def ffn_res(x, w1, b1, w2, b2) -> Tuple[Tensor, Tensor]:
+def ffn_res(x, w1, b1, w2, b2, recompute_h: bool = False) -> Tuple[Tensor, Tensor]:
     """(ffn(x, ...), x) -- the second value feeds the residual add behind the FFN (see LinearFn)."""
     if x.dtype == torch.bfloat16:
+        if recompute_h:
+            raise NotImplementedError(_NO_BF16_RECOMPUTE_H)
         return FFNBf16Fn.apply(x, w1, b1, w2, b2, True)
+    if recompute_h:
+        return FFNFn.apply(x, w1, b1, w2, b2, True, True)
     return FFNFn.apply(x, w1, b1, w2, b2, True)
 
 

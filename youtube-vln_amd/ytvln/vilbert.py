@@ -20,6 +20,7 @@ GPU only: tensors must be on a HIP device; there is no CPU path (use `oracle/` f
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import json
 import logging
@@ -104,6 +105,7 @@ class BertConfig:
 # ------------------------------------------------------------------------------------------------------------------
 class _Runtime:
     drop: Optional[DropoutState] = None
+    ffn_recompute: bool = False          # BertEncoder.recompute == "ffn", for the duration of that encoder's forward (read by _ffn_block)
 
 
 def _begin_forward(module: nn.Module, device) -> None:
@@ -131,6 +133,90 @@ def _share_drop_state() -> None:
         t.record_stream(ts.side_stream(t.device))
         if ts.main is not None:
             t.record_stream(ts.main)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# activation recomputation (BertEncoder.recompute): opt-in, bit-exact
+# ------------------------------------------------------------------------------------------------------------------
+RECOMPUTE_TIERS = ("none", "ffn", "layer")
+
+
+@contextlib.contextmanager
+def _replay_drop(state, site: int):
+    """Install `state` -- the DropoutState OBJECT a segment recorded when it first ran -- as _Runtime.drop with its site counter rewound to
+    `site`, the counter's value on entry to that first run: the body then asks for the same (rng tensor, site) pairs in the same order and
+    every dropout kernel draws the masks of the forward.  Whatever was installed before comes back afterwards, and so does the counter, also
+    when the body raises.  The recorded object is used, never the _Runtime.drop of the moment: by the time a backward pass recomputes,
+    another forward (a second model, the next micro-step) may have replaced it."""
+    prev = _Runtime.drop
+    back = None if state is None else state._site
+    if state is not None:
+        state._site = int(site)
+    _Runtime.drop = state
+    try:
+        yield state
+    finally:
+        _Runtime.drop = prev
+        if state is not None:
+            state._site = back
+
+
+class _RecomputeLayerFn(torch.autograd.Function):
+    """One encoder layer (text, image or connection) as ONE autograd node that keeps only its inputs (recompute = "layer").
+
+    forward: runs `fn(*hidden, *rest)` with gradients off (a Function's forward always does) -- the same launches on the same inputs as the
+    plain layer, and the dropout site counter advances exactly as it does there, so every site after the layer keeps its id.  It records the
+    DropoutState object of this forward and the counter's value on entry.
+    backward: re-runs `fn` with gradients on under _replay_drop (same kernels, same inputs, same masks: the same bits), then sends the incoming
+    gradients through that sub-graph.  Parameter gradients are accumulated by the inner backward itself (arena-direct writes happen once,
+    there; post-accumulate hooks fire from there, once); the node returns the gradients of the hidden states only.  The parameters are NOT
+    inputs of the node (their AccumulateGrad nodes would run a second time from the outer graph and fire every hook twice); `anchor`, an
+    empty leaf that requires a gradient and never gets one, is: the node then takes part in a backward pass whose hidden states carry no
+    gradient (a frozen prefix below it).
+    The recomputation runs on the stream the engine gives the node -- the stream of its forward -- with two-stream mode off: a connection
+    layer, which spans both sides, is recomputed on one stream (bit-identical, see ops.TwoStream)."""
+
+    @staticmethod
+    def forward(ctx, fn, n_hidden, anchor, *tensors):
+        ctx.set_materialize_grads(False)
+        ctx.fn, ctx.n_hidden = fn, n_hidden
+        st = _Runtime.drop
+        ctx.site = st._site if st is not None else 0
+        out = fn(*tensors)
+        ctx.drop = st if st is not None else _Runtime.drop          # (a bare encoder: the state is created by the first dropout site, counter 0)
+        ctx.is_tensor = [torch.is_tensor(t) for t in tensors]
+        ctx.other = [None if torch.is_tensor(t) else t for t in tensors]
+        ctx.save_for_backward(*[t for t in tensors if torch.is_tensor(t)])
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        it = iter(ctx.saved_tensors)
+        tensors = [next(it) if is_t else o for is_t, o in zip(ctx.is_tensor, ctx.other)]
+        cur = torch.cuda.current_stream()
+        for t in tensors:          # a connection layer reads, on this stream, hidden states the other stream produced
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(cur)
+        hidden = [t.detach().requires_grad_(ctx.needs_input_grad[3 + i]) for i, t in enumerate(tensors[:ctx.n_hidden])]
+        ts = ops.TwoStream
+        was_active, ts.active = ts.active, False
+        try:
+            with torch.enable_grad(), _replay_drop(ctx.drop, ctx.site):
+                out = ctx.fn(*hidden, *tensors[ctx.n_hidden:])
+        finally:
+            ts.active = was_active
+        out = out if isinstance(out, tuple) else (out,)
+        pairs = [(o, g) for o, g in zip(out, grads) if g is not None and o.requires_grad]
+        if pairs:
+            torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
+        return (None, None, None) + tuple(h.grad for h in hidden) + (None,) * (len(ctx.needs_input_grad) - 3 - ctx.n_hidden)
+
+
+def _recompute_layer(fn, hidden, rest):
+    """`fn(*hidden, *rest)` -> a tensor or a tuple of tensors, as one recomputed node.  `hidden`: the hidden states (differentiated);
+    `rest`: masks and flags (not differentiated)."""
+    anchor = torch.empty(0, device=hidden[0].device, requires_grad=True)
+    return _RecomputeLayerFn.apply(fn, len(hidden), anchor, *hidden, *rest)
 
 
 def _p(module: nn.Module, p: float) -> float:
@@ -345,7 +431,10 @@ class BertOutput(_OutputBase):
 def _ffn_block(inter: _IntermediateBase, out: _OutputBase, x):
     """intermediate -> output of a layer, with the two GEMMs and the GELU fused in one autograd node when possible."""
     if _act_name(inter.intermediate_act_fn) == "gelu":
-        h, residual = ops.ffn_res(x, inter.dense.weight, inter.dense.bias, out.dense.weight, out.dense.bias)
+        if _Runtime.ffn_recompute:          # recompute = "ffn": keep z, rebuild h = gelu(z) in the backward (fp32 only: bf16 hidden states raise)
+            h, residual = ops.ffn_res(x, inter.dense.weight, inter.dense.bias, out.dense.weight, out.dense.bias, recompute_h=True)
+        else:
+            h, residual = ops.ffn_res(x, inter.dense.weight, inter.dense.bias, out.dense.weight, out.dense.bias)
         return _add_ln(out.LayerNorm, h, residual, out, p_pre=out.dropout.p)
     return out(inter(x), x)
 
@@ -533,6 +622,15 @@ class BertEncoder(nn.Module):
     # local of its forward (vilbert.py:736), and False -- parity with it -- is the default here.  Set `encoder.use_co_attention_mask = True` to
     # hand `co_attention_mask` to every connection layer (BertBiAttention adds it to the scores, vilbert.py:581-582, 603-604).
     use_co_attention_mask = False
+    # Extension, opt-in (same standing as the switch above: a plain attribute, not a config field): activation recomputation.
+    #   "none"   every activation the backward needs is kept (default: nothing changes).
+    #   "ffn"    the fused FFN nodes keep the GELU pre-activation z and rebuild h = gelu(z) in their backward with ytvln_gelu_fwd_f32:
+    #            rows x intermediate x 4 bytes less per FFN, one elementwise launch more.  fp32 hidden states with "gelu"; "relu" and "swish"
+    #            layers are accepted and unchanged (relu keeps only its output; swish is out of scope); bf16 hidden states raise.
+    #   "layer"  every text, image and connection layer that runs with gradients becomes one autograd node that keeps only its inputs and
+    #            re-runs the layer in the backward, with the dropout masks of the forward replayed from the recorded (DropoutState, site).
+    # Losses, gradients and updated parameters are bit-identical to "none" in every tier.  Inert in eval mode and under torch.no_grad().
+    recompute = "none"
 
     def __init__(self, config):
         super().__init__()
@@ -575,20 +673,38 @@ class BertEncoder(nn.Module):
                 output_all_encoded_layers=True, output_all_attention_masks=False):
         """Interleaving schedule of vilbert.py:737-811: for each (v_id, t_id) pair run the pending image layers, the
         pending text layers, then co-attention layer `count`; finally the remaining layers of both streams."""
+        tier = self._recompute_tier(output_all_attention_masks)
         self._set_probs(bool(output_all_attention_masks))
         ts = ops.TwoStream
         if self.in_batch_pairs or self.FAST_MODE:
             ts.end(txt_embedding)                        # these modes rebuild the text rows from the image batch: one stream
         else:
             ts.begin(txt_embedding.device)               # (no-op when BertModel.forward opened the region or the mode is off)
+        was_ffn, _Runtime.ffn_recompute = _Runtime.ffn_recompute, tier == "ffn"
         try:
             return self._forward(txt_embedding, image_embedding, txt_attention_mask, image_attention_mask, co_attention_mask,
-                                 output_all_encoded_layers, output_all_attention_masks)
+                                 output_all_encoded_layers, output_all_attention_masks, tier == "layer")
         finally:
             ts.active = False
+            _Runtime.ffn_recompute = was_ffn
+
+    def _recompute_tier(self, output_all_attention_masks) -> str:
+        """The tier this forward runs with: `recompute`, validated, or "none" where the setting is inert (eval mode, gradients off)."""
+        tier = self.recompute
+        if tier not in RECOMPUTE_TIERS:
+            raise ValueError(f"BertEncoder.recompute = {tier!r}: expected one of {RECOMPUTE_TIERS}")
+        if tier == "none" or not self.training or not torch.is_grad_enabled():
+            return "none"
+        if self.cut_after:
+            raise NotImplementedError(f"BertEncoder.recompute = {tier!r} with autograd cut points (encoder.cut_after, the phased graph-replayed "
+                                      'step): a recomputing backward is not captured; run it with recompute = "none"')
+        if tier == "layer" and output_all_attention_masks:
+            raise NotImplementedError('BertEncoder.recompute = "layer" with output_all_attention_masks=True: the attention probabilities are an '
+                                      'inspection output the recomputed node does not return; run it with recompute = "none"')
+        return tier
 
     def _forward(self, txt_embedding, image_embedding, txt_attention_mask, image_attention_mask, co_attention_mask,
-                 output_all_encoded_layers, output_all_attention_masks):
+                 output_all_encoded_layers, output_all_attention_masks, recompute_layers=False):
         ts = ops.TwoStream
         v_start = t_start = 0
         all_t, all_v, att_t, att_v, att_c = [], [], [], [], []
@@ -600,6 +716,10 @@ class BertEncoder(nn.Module):
                 if idx < frozen_to:
                     with torch.no_grad():
                         x, pr = layers[idx](x, mask)
+                elif recompute_layers:
+                    # (a trainable per-score mask is differentiated like the hidden states; a constant one is carried along)
+                    x, pr = _recompute_layer(lambda h, m, layer=layers[idx]: layer(h, m)[0],
+                                             *(((x, mask), ()) if mask.requires_grad else ((x,), (mask,)))), None
                 else:
                     x, pr = layers[idx](x, mask)
                 if cuts:
@@ -629,7 +749,14 @@ class BertEncoder(nn.Module):
                 txt_embedding = txt_embedding.expand(nb, txt_embedding.size(1), txt_embedding.size(2)).contiguous()
                 txt_attention_mask = txt_attention_mask.reshape(txt_attention_mask.shape[0], -1).expand(nb, txt_embedding.size(1)).contiguous().view(
                     nb, 1, 1, txt_embedding.size(1))
-            if self.with_coattention:
+            if self.with_coattention and recompute_layers:
+                c_layer, use_co = self.c_layer[count], bool(self.use_co_attention_mask)
+                co_grad = torch.is_tensor(co_attention_mask) and co_attention_mask.requires_grad          # a trainable co_attention_mask
+                image_embedding, txt_embedding = _recompute_layer(
+                    lambda hv, ht, co, mv, mt, layer=c_layer, use_co=use_co: layer(hv, mv, ht, mt, co, use_co)[:2],
+                    (image_embedding, txt_embedding) + ((co_attention_mask,) if co_grad else ()),
+                    (() if co_grad else (co_attention_mask,)) + (image_attention_mask, txt_attention_mask))
+            elif self.with_coattention:
                 image_embedding, txt_embedding, co_probs = self.c_layer[count](
                     image_embedding, image_attention_mask, txt_embedding, txt_attention_mask, co_attention_mask,
                     bool(self.use_co_attention_mask))
@@ -856,6 +983,11 @@ class BertModel(BertPreTrainedModel):
         self.t_pooler = BertTextPooler(config)
         self.v_pooler = BertImagePooler(config)
         self.apply(self.init_bert_weights)
+        # activation recomputation is an attribute of the encoder; a run that carries its settings in `config.args` (as get_optimization reads
+        # args.max_grad_norm) switches it on with args.recompute.  No such field: the attribute keeps its default.
+        args = getattr(config, "args", None)
+        if args is not None and hasattr(args, "recompute"):
+            self.encoder.recompute = args.recompute
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
                 co_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
