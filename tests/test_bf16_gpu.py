@@ -339,7 +339,7 @@ def test_loss_gradients_bf16_and_adamw_copy(dev, lib):
     if gb.stride(0) != V:          # (autograd may repack the gradient; when it keeps the kernel's buffer the padding must be zero)
         full = torch.as_strided(gb, (M, gb.stride(0)), (gb.stride(0), 1))
         assert float(full[:, V:].float().abs().max()) == 0.0, "padding columns must be zero (YTVLN_GEMM_A_ZERO_PADDED contract)"
-    # the gradient buffer as the kernel leaves it (what LinearBf16Fn.backward receives)
+    # the gradient buffer as the kernel leaves it (what LinearFn.backward receives on the bf16-resident path)
     dl, ldd = ops._alloc_rows_bf16(M, V, dev)
     row_lse = torch.empty(M, device=dev); row_loss = torch.empty(M, device=dev); out = torch.empty(2, device=dev)
     one = torch.ones(1, device=dev)

@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import ACT_SWISH, EPI_GELU, EPI_MUL_DGELU, EPI_NONE, EPI_RELU, GEMM_A_ZERO_PADDED, GEMM_SPLIT_BF16X3, call
 
 Tensor = torch.Tensor
-# "swish" is not a GEMM epilogue: the projection runs with EPI_NONE and ytvln_act_fwd_* follows (LinearFn / LinearBf16Fn)
+# "swish" is not a GEMM epilogue: the projection runs with EPI_NONE and ytvln_act_fwd_* follows (LinearFn, either format)
 _ACT = {"none": EPI_NONE, None: EPI_NONE, "gelu": EPI_GELU, "relu": EPI_RELU, "swish": ACT_SWISH}
 
 
@@ -45,29 +45,6 @@ def _check(t: Tensor, name: str, dtype=torch.float32):
         raise RuntimeError(f"ytvln.ops: `{name}` must live on the GPU (no CPU fallback); got device {t.device}")
     if t.dtype != dtype:
         raise RuntimeError(f"ytvln.ops: `{name}` must be {dtype}; got {t.dtype}")
-
-
-def _rows2d(x: Tensor, name: str) -> Tuple[Tensor, int, int, int]:
-    """View x as [M, K] rows with unit inner stride; returns (tensor-keeping-storage, M, K, leading dimension)."""
-    _check(x, name)
-    K = x.shape[-1]
-    if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= K:
-        return x, x.shape[0], K, x.stride(0)
-    if not x.is_contiguous():
-        x = x.contiguous()
-    return x, x.numel() // max(K, 1), K, K
-
-
-def _rows2d_any(x: Tensor) -> Tuple[Tensor, int, int, int]:
-    """_rows2d without the fp32 check (bf16 logits of the bf16-resident path; rows may carry a padded leading dimension)."""
-    if not x.is_cuda:
-        raise RuntimeError("ytvln.ops: tensor must live on the GPU")
-    K = x.shape[-1]
-    if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= K:
-        return x, x.shape[0], K, x.stride(0)
-    if not x.is_contiguous():
-        x = x.contiguous()
-    return x, x.numel() // max(K, 1), K, K
 
 
 def _i64(t: Tensor, name: str) -> Tensor:
@@ -514,20 +491,6 @@ def _pad_ld(n: int) -> int:
     return (n + 31) // 32 * 32 if (n >= 1024 and n % 32) else n
 
 
-def _alloc_rows(M: int, N: int, device, zero_pad: bool = False):
-    """[M, N] fp32 view with leading dimension _pad_ld(N); with zero_pad the pad columns are cleared and remembered."""
-    ld = _pad_ld(N)
-    if ld == N:
-        return torch.empty((M, N), dtype=torch.float32, device=device), N
-    full = torch.empty((M, ld), dtype=torch.float32, device=device)
-    if zero_pad:
-        full[:, N:].zero_()
-        key = full.untyped_storage().data_ptr()
-        _ZERO_PADDED[key] = ld
-        _weakref.finalize(full, _ZERO_PADDED.pop, key, None)      # `full` stays alive as the base of the returned view
-    return full[:, :N], ld
-
-
 def _view_rows_as(rows: Tensor, ld: int, shape):
     """View a [M, N] row buffer with leading dimension ld as `shape` (= (*lead, N))."""
     shape = tuple(shape)
@@ -540,17 +503,6 @@ def _view_rows_as(rows: Tensor, ld: int, shape):
     return torch.as_strided(rows, shape, tuple(reversed(strides)) + (1,))
 
 
-def _rows_of_grad(dy: Tensor, M: int, N: int):
-    """(dy as [M, N] rows, leading dimension, GEMM flags): keeps a padded-leading-dimension gradient in place."""
-    d2 = dy.reshape(M, N)
-    if d2.stride(1) == 1 and d2.stride(0) > N and d2.stride(0) % 4 == 0 and d2.data_ptr() % 16 == 0:
-        known = _ZERO_PADDED.get(d2.untyped_storage().data_ptr()) == d2.stride(0) and d2.storage_offset() == 0
-        return d2, d2.stride(0), (GEMM_A_ZERO_PADDED if known else 0), known
-    if not d2.is_contiguous():
-        d2 = d2.contiguous()
-    return d2, N, 0, False
-
-
 def _overlaps(a: Tensor, b: Tensor) -> bool:
     if a is None or b is None or a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
         return False
@@ -558,21 +510,146 @@ def _overlaps(a: Tensor, b: Tensor) -> bool:
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def _accumulate_target(dres, M: int, K: int, *live):
-    """The [M, K] row view of a residual-branch gradient the input-gradient GEMM may accumulate into (beta = 1), or None.
-    `live`: tensors this backward still reads (the output gradient): with dropout p = 0 AddLayerNormFn hands the SAME storage to the
-    sublayer-output gradient and to the residual gradient, and accumulating in place would overwrite an operand that is being read
-     -- the caller then falls back to a separate buffer + add."""
-    if dres is None or dres.dtype != torch.float32 or not dres.is_cuda or dres.numel() != M * K or not dres.is_contiguous():
-        return None
-    if any(_overlaps(dres, t) for t in live):
-        return None
-    return dres.view(M, K)
+# ------------------------------------------------------------------------------------------------------------------
+# the two storage formats of a hidden state.  LinearFn, FFNFn, AddLayerNormFn and _ln_bwd are written once against this description:
+# everything that depends on whether rows are fp32 or bf16-resident (set_matmul_precision) is a member here and nowhere else.
+# ------------------------------------------------------------------------------------------------------------------
+class RowFormat:
+    """fp32 rows -- the reference's arithmetic.  Operands are read where they lie; any leading dimension goes."""
+    dtype = torch.float32
+    suffix = "f32"                  # of ytvln_act_fwd_* / ytvln_act_bwd_* / ytvln_ln_fwd_* / ytvln_ln_bwd_*
+    row_align = 1                   # elements: a strided row view is used in place when its leading dimension and address are multiples of this
+    ln_bwd_f32_copy = False         # ytvln_ln_bwd_<suffix> takes a pointer for an fp32 copy of ds (rows that are fp32 serve as they are)
+    exact_gelu_replay = True        # gelu(stored z) is the stored h bit for bit: FFNFn's `recompute_h` tier exists
+
+    def gemm(self, *args, **kw):
+        """(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, **keywords).  Through the module attribute at call time: a timer may replace it."""
+        return _gemm(*args, **kw)
+
+    def empty(self, M: int, N: int, device) -> Tensor:
+        return torch.empty((M, N), dtype=self.dtype, device=device)
+
+    def cast(self, t: Tensor) -> Tensor:
+        """t in this format."""
+        return t
+
+    def rows(self, x: Tensor, name: str) -> Tuple[Tensor, int, int, int]:
+        """View x as [M, K] rows with unit inner stride; returns (tensor-keeping-storage, M, K, leading dimension)."""
+        _check(x, name, self.dtype)
+        K, a = x.shape[-1], self.row_align
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % a == 0 and x.data_ptr() % (a * x.element_size()) == 0:
+            return x, x.shape[0], K, x.stride(0)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        return x, x.numel() // max(K, 1), K, K
+
+    def pad_ld(self, n: int) -> int:
+        return _pad_ld(n)
+
+    def alloc_rows(self, M: int, N: int, device, zero_pad: bool = False, kernel_zeroes_pad: bool = False):
+        """[M, N] view with leading dimension pad_ld(N).  The pad columns are cleared here (`zero_pad`) or by the kernel the caller is about to
+        launch (`kernel_zeroes_pad`) and then remembered as zero, or left as they are."""
+        ld = self.pad_ld(N)
+        if ld == N:
+            return self.empty(M, N, device), N
+        full = self.empty(M, ld, device)
+        if zero_pad:
+            full[:, N:].zero_()
+        if zero_pad or kernel_zeroes_pad:
+            key = full.untyped_storage().data_ptr()
+            _ZERO_PADDED[key] = ld
+            _weakref.finalize(full, _ZERO_PADDED.pop, key, None)      # `full` stays alive as the base of the returned view
+        return full[:, :N], ld
+
+    def grad_rows(self, dy: Tensor, M: int, N: int):
+        """(dy as [M, N] rows, leading dimension, GEMM flags): keeps a padded-leading-dimension gradient in place."""
+        d2 = dy.reshape(M, N)
+        if d2.stride(1) == 1 and d2.stride(0) > N and d2.stride(0) % 4 == 0 and d2.data_ptr() % 16 == 0:
+            known = _ZERO_PADDED.get(d2.untyped_storage().data_ptr()) == d2.stride(0) and d2.storage_offset() == 0
+            return d2, d2.stride(0), (GEMM_A_ZERO_PADDED if known else 0)
+        if not d2.is_contiguous():
+            d2 = d2.contiguous()
+        return d2, N, 0
+
+    def weight(self, w: Tensor) -> Tuple[Tensor, int]:
+        """(the GEMM operand that stands for the [out, in] master weight w, its leading dimension)."""
+        return w, w.stride(0)
+
+    def f32_rows(self, rows: Tensor, ld: int, N: int) -> Tuple[Tensor, int]:
+        """(fp32 view or copy of [M, N] rows, its leading dimension) for `colsum`, where a bias gradient could not ride on the dW launch."""
+        return rows, ld
+
+    def accumulate_target(self, dres, M: int, K: int, *live):
+        """The [M, K] row view of a residual-branch gradient the input-gradient GEMM may accumulate into (beta = 1), or None.
+        `live`: tensors this backward still reads or that its caller may still hold (the output gradient): with dropout p = 0 AddLayerNormFn
+        hands the SAME storage to the sublayer-output gradient and to the residual gradient, and accumulating in place would overwrite an
+        operand that is being read -- the caller then falls back to a separate buffer + add."""
+        if dres is None or dres.dtype != self.dtype or not dres.is_cuda or dres.numel() != M * K or not dres.is_contiguous():
+            return None
+        if any(_overlaps(dres, t) for t in live):
+            return None
+        return dres.view(M, K)
+
+
+class _Bf16RowFormat(RowFormat):
+    """The bf16-resident path (BASELINE configs[4]; set_matmul_precision("bf16")): hidden states and their gradients are bf16 rows of 8-element
+    (16-byte) granularity, a GEMM reads the bf16 copy of a weight, and padding up to a leading dimension must be ZERO."""
+    dtype = torch.bfloat16
+    suffix = "bf16"
+    row_align = 8
+    ln_bwd_f32_copy = True
+    exact_gelu_replay = False       # z is stored rounded to bf16, and bf16(gelu(float(bf16 z))) is not the stored h
+
+    def gemm(self, *args, **kw):
+        return _gemm_bf16(*args, **kw)
+
+    def cast(self, t: Tensor) -> Tensor:
+        """fp32 values entering the path (network inputs, gradients coming back from the fp32 heads) are rounded once."""
+        return cast_bf16(t) if t.dtype == torch.float32 else t
+
+    def pad_ld(self, n: int) -> int:
+        return _pad8(n)
+
+    def grad_rows(self, dy: Tensor, M: int, N: int):
+        """bf16 gradients with a padded leading dimension come from the loss kernels (ytvln_ce_bwd_bf16 / ytvln_kl_bwd_bf16: zero padding written
+        by the kernel) and are used in place; fp32 gradients (the small heads on the pooled vectors) are cast; anything unaligned is repacked
+        into a zero-padded buffer."""
+        d2 = self.cast(dy.reshape(M, N)).reshape(M, N)
+        if d2.stride(1) == 1 and d2.stride(0) % 8 == 0 and d2.data_ptr() % 16 == 0 and (d2.stride(0) == N or
+                                                                                       _ZERO_PADDED.get(d2.untyped_storage().data_ptr()) == d2.stride(0)):
+            return d2, d2.stride(0), (GEMM_A_ZERO_PADDED if d2.stride(0) != N else 0)
+        ld = _pad8(N)
+        if ld == N:
+            return d2.contiguous(), N, 0
+        full = torch.zeros((M, ld), dtype=self.dtype, device=dy.device)
+        full[:, :N].copy_(d2)
+        return full[:, :N], ld, GEMM_A_ZERO_PADDED
+
+    def weight(self, w: Tensor) -> Tuple[Tensor, int]:
+        return _bf16_weight(w), w.shape[1]
+
+    def f32_rows(self, rows: Tensor, ld: int, N: int) -> Tuple[Tensor, int]:
+        return (rows.float() if ld == N else rows.contiguous().float()), N
+
+
+_F32, _B16 = RowFormat(), _Bf16RowFormat()
+
+
+def _format_of(t: Tensor) -> RowFormat:
+    return _B16 if t.dtype == torch.bfloat16 else _F32
+
+
+def _alloc_rows_bf16(M: int, N: int, device):
+    """A bf16 gradient buffer as the loss kernels are handed it: they write zeros into the padding."""
+    return _B16.alloc_rows(M, N, device, kernel_zeroes_pad=True)
 
 
 class LinearFn(torch.autograd.Function):
-    """y = act(x W^T + b)  -- nn.Linear + optional erf-GELU / ReLU epilogue, all on the fp32 MFMA GEMM; act = "swish" is the plain GEMM
-    followed by the elementwise kernel ytvln_act_fwd_f32 (unfused by design: one extra read and write of [M, N]).
+    """y = act(x W^T + b)  -- nn.Linear + optional erf-GELU / ReLU epilogue on the GEMM of `fmt` (default: fp32 rows on the fp32 MFMA GEMM, whatever
+    the precision mode); act = "swish" is the plain GEMM followed by the elementwise kernel ytvln_act_fwd_* (unfused by design: one extra read and
+    write of [M, N]).  On bf16 rows x is a bf16 hidden state (or an fp32 network input, cast once), W the bf16 copy of the fp32 master weight and
+    y bf16, or fp32 when `out_fp32` (pooled vectors); dW and db are fp32 in either format and go straight into the gradient arena; db rides on the
+    dW launch.
 
     `passthrough=True` returns (y, x): the second output is x itself, to be used by the RESIDUAL connection that skips the sublayer this
     projection opens (vilbert.py:322-325, 365-368: `LayerNorm(dropout(dense(...)) + input_tensor)`).  The residual branch's gradient then
@@ -580,79 +657,93 @@ class LinearFn(torch.autograd.Function):
     launching a separate elementwise add for the fan-out of x."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act, passthrough=False):
+    def forward(ctx, x, weight, bias, act, passthrough=False, fmt=_F32, out_fp32=False):
         ctx.set_materialize_grads(False)
-        ctx.passthrough = bool(passthrough)
-        x2, M, K, lda = _rows2d(x, "x")
+        ctx.passthrough, ctx.fmt = bool(passthrough), fmt
+        xf = fmt.cast(x)
+        ctx.x_was_f32 = xf is not x          # an fp32 input of the bf16-resident path: cast on entry, and its gradient leaves as fp32
+        x2, M, K, lda = fmt.rows(xf, "x")
         _check(weight, "weight")
         if weight.stride(-1) != 1:
             weight = weight.contiguous()
         N = weight.shape[0]
         assert weight.shape[1] == K, (weight.shape, K)
+        out = _F32 if out_fp32 else fmt          # `out_fp32`: the output leaves the bf16-resident path as fp32
         need_grad = any(ctx.needs_input_grad)
         epi = _ACT[act]
+        dev = x.device
         if epi == ACT_SWISH:          # unfused: the plain GEMM writes the pre-activation z (kept for the backward), then y = z * sigmoid(z)
-            z, ldy = torch.empty((M, N), dtype=torch.float32, device=x.device), N
-            _gemm(x2, lda, 0, weight, weight.stride(0), 1, z, N, M, N, K, bias=bias)
+            z, ldy = fmt.empty(M, N, dev), N
+            fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, z, N, M, N, K, bias=bias)
             y = torch.empty_like(z) if need_grad else z          # nothing to keep without a backward: in place
-            call("ytvln_act_fwd_f32", _ptr(z), _ptr(y), M * N, ACT_SWISH, _stream())
+            call("ytvln_act_fwd_" + fmt.suffix, _ptr(z), _ptr(y), M * N, ACT_SWISH, _stream())
+            if out is not fmt:
+                y = y.float()
         else:
-            if epi == EPI_NONE:
-                y, ldy = _alloc_rows(M, N, x.device)          # wide odd widths (logits) get a 32-float aligned leading dimension
-            else:
-                y, ldy = torch.empty((M, N), dtype=torch.float32, device=x.device), N
-            z = torch.empty_like(y) if (epi == EPI_GELU and need_grad) else None
-            _gemm(x2, lda, 0, weight, weight.stride(0), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
+            if out is _F32 and (epi == EPI_NONE or out is not fmt):
+                y, ldy = _F32.alloc_rows(M, N, dev)          # wide odd widths (logits) get a 32-float aligned leading dimension
+            else:          # (an fp32 activation output stays dense: the ReLU backward reads it as its aux)
+                y, ldy = out.empty(M, N, dev), N
+            z = fmt.empty(M, N, dev) if (epi == EPI_GELU and need_grad) else None
+            fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
         ctx.epi, ctx.dims, ctx.lda, ctx.has_bias = epi, (M, N, K), lda, bias is not None
         ctx.in_shape = x.shape
         ctx.targets = _targets_of(weight)
         ctx.btargets = _targets_of(bias) if bias is not None else None
-        ctx.save_for_backward(x2, weight, z if epi in (EPI_GELU, ACT_SWISH) else (y if epi == EPI_RELU else None))
+        # the ReLU backward needs the sign of the OUTPUT: a bf16 copy of it when the output itself leaves as fp32
+        aux = z if epi in (EPI_GELU, ACT_SWISH) else ((y if out is fmt else fmt.cast(y)) if (epi == EPI_RELU and need_grad) else None)
+        ctx.save_for_backward(x2, weight, aux)
         out = _view_rows_as(y, ldy, tuple(x.shape[:-1]) + (N,))
         return (out, x) if ctx.passthrough else out
 
     @staticmethod
     def backward(ctx, dy, dres=None):
+        tail = (None,) * (len(ctx.needs_input_grad) - 3)          # act, passthrough, fmt, out_fp32: as many as the call passed
         if dy is None:
-            return (dres if ctx.needs_input_grad[0] else None), None, None, None, None
+            return ((dres if ctx.needs_input_grad[0] else None), None, None) + tail
+        fmt = ctx.fmt
         x2, weight, aux = ctx.saved_tensors
         M, N, K = ctx.dims
+        dy_in = dy
+        dy, ldy, flags = fmt.grad_rows(dy, M, N)
         if ctx.epi != EPI_NONE:
-            dy = dy.reshape(M, N)
-            if not dy.is_contiguous():
-                dy = dy.contiguous()
-            dz = torch.empty_like(dy)
-            call("ytvln_act_bwd_f32", _ptr(dy), _ptr(aux), _ptr(dz), dy.numel(), ctx.epi, _stream())
-            dy, ldy, flags = dz, N, 0
-        else:
-            dy, ldy, flags, _ = _rows_of_grad(dy, M, N)
+            if ldy != N:
+                dy, ldy, flags = dy.contiguous(), N, 0
+            dz = fmt.empty(M, N, dy.device)
+            call("ytvln_act_bwd_" + fmt.suffix, _ptr(dy), _ptr(aux), _ptr(dz), M * N, ctx.epi, _stream())
+            dy = dz
+        dev = dy.device
         dx = dw = db = None
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if want_db:
             db = _direct_grad(ctx.btargets, (N,))
             if db is None:
-                db = torch.empty(N, dtype=torch.float32, device=dy.device)
+                db = torch.empty(N, dtype=torch.float32, device=dev)
         db_done = False
         if ctx.needs_input_grad[0]:
-            acc = _accumulate_target(dres, M, K, dy)
+            w, ldw = fmt.weight(weight)
+            acc = fmt.accumulate_target(dres, M, K, dy, dy_in)
             if acc is not None:          # dx = d(residual) + dY W, written over the residual branch's gradient
-                _gemm(dy, ldy, 0, weight, weight.stride(0), 0, acc, K, M, K, N, beta=1.0, flags=flags)
+                fmt.gemm(dy, ldy, 0, w, ldw, 0, acc, K, M, K, N, beta=1.0, flags=flags)
                 dx = acc.view(ctx.in_shape)
             else:
-                dx = torch.empty((M, K), dtype=torch.float32, device=dy.device)
-                _gemm(dy, ldy, 0, weight, weight.stride(0), 0, dx, K, M, K, N, flags=flags)
+                dx = fmt.empty(M, K, dev)
+                fmt.gemm(dy, ldy, 0, w, ldw, 0, dx, K, M, K, N, flags=flags)
                 dx = dx.view(ctx.in_shape)
                 if dres is not None:
                     dx = dx + dres.reshape(ctx.in_shape)
+                if ctx.x_was_f32:
+                    dx = dx.float()
         if ctx.needs_input_grad[1]:
             dw = _direct_grad(ctx.targets, (N, K))
             if dw is None:
-                dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
-            # db = column sums of dY = row sums of the A operand (dY^T) of this launch: rides on the GEMM when it can
-            db_done = _gemm(dy, ldy, 1, x2, ctx.lda, 0, dw, K, N, K, M, flags=flags, rowsum=db if want_db else None)
+                dw = torch.empty((N, K), dtype=torch.float32, device=dev)
+            # dW[N, K] = dY^T X; db = column sums of dY = row sums of the A operand (dY^T) of this launch: rides on the GEMM when it can
+            db_done = fmt.gemm(dy, ldy, 1, x2, ctx.lda, 0, dw, K, N, K, M, flags=flags, rowsum=db if want_db else None)
         if want_db and not db_done:
-            colsum(dy, M, N, ldy, out=db)
-        return dx, dw, db, None, None
+            d32, ld32 = fmt.f32_rows(dy, ldy, N)
+            colsum(d32, M, N, ld32, out=db)
+        return (dx, dw, db) + tail
 
 
 def _wants_bf16(x: Tensor, weight: Tensor) -> bool:
@@ -666,39 +757,37 @@ def _wants_bf16(x: Tensor, weight: Tensor) -> bool:
 
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, act: Optional[str] = None, out_fp32: bool = False) -> Tensor:
     """`out_fp32` only matters on the bf16-resident path: the output leaves the path as fp32 (the pooled vectors and the small heads on them)."""
-    if _wants_bf16(x, weight):
-        return LinearBf16Fn.apply(x, weight, bias, act, False, out_fp32)
-    return LinearFn.apply(x, weight, bias, act)
+    return LinearFn.apply(x, weight, bias, act, False, _B16 if _wants_bf16(x, weight) else _F32, out_fp32)
 
 
 def linear_res(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, act: Optional[str] = None) -> Tuple[Tensor, Tensor]:
     """(linear(x, ...), x): use the second value for the residual connection around the sublayer (see LinearFn)."""
-    if _wants_bf16(x, weight):
-        return LinearBf16Fn.apply(x, weight, bias, act, True, False)
-    return LinearFn.apply(x, weight, bias, act, True)
+    return LinearFn.apply(x, weight, bias, act, True, _B16 if _wants_bf16(x, weight) else _F32)
 
 
 class FFNFn(torch.autograd.Function):
     """out = gelu(x W1^T + b1) W2^T + b2   (BertIntermediate + BertOutput.dense, vilbert.py:351-354, 365).
-    Backward fuses the GELU derivative into the epilogue of the dX GEMM of the second projection.
+    Backward fuses the GELU derivative into the epilogue of the dX GEMM of the second projection.  x, the GELU pre-activation z, the hidden h and
+    out are rows of `fmt`; weight and bias gradients are fp32.
 
-    `recompute_h=True` (BertEncoder.recompute = "ffn"): the node keeps the pre-activation z and not h = gelu(z) -- M x I x 4 bytes less per FFN
+    `recompute_h=True` (BertEncoder.recompute = "ffn"; fp32 rows only, see `ffn`): the node keeps the pre-activation z and not h = gelu(z) -- M x I x 4 bytes less per FFN
     between forward and backward -- and its backward rebuilds h with ytvln_gelu_fwd_f32 (the epilogue's own device function on the stored z:
     the same bits) into a buffer that lives from just before the dW2 GEMM to just after it.  Everything else is the default path."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, passthrough=False, recompute_h=False):
+    def forward(ctx, x, w1, b1, w2, b2, passthrough=False, recompute_h=False, fmt=_F32):
         ctx.set_materialize_grads(False)
-        ctx.passthrough = bool(passthrough)
+        ctx.passthrough, ctx.fmt = bool(passthrough), fmt
         ctx.recompute_h = bool(recompute_h)
-        x2, M, K, lda = _rows2d(x, "x")
+        x2, M, K, lda = fmt.rows(x, "x")
         I, N = w1.shape[0], w2.shape[0]
         need_grad = any(ctx.needs_input_grad)
-        h = torch.empty((M, I), dtype=torch.float32, device=x.device)
-        z = torch.empty_like(h) if need_grad else None
-        _gemm(x2, lda, 0, w1, w1.stride(0), 1, h, I, M, I, K, bias=b1, aux=z, ldaux=I, epi=EPI_GELU)
-        y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-        _gemm(h, I, 0, w2, w2.stride(0), 1, y, N, M, N, I, bias=b2)
+        dev = x.device
+        h = fmt.empty(M, I, dev)
+        z = fmt.empty(M, I, dev) if need_grad else None
+        fmt.gemm(x2, lda, 0, *fmt.weight(w1), 1, h, I, M, I, K, bias=b1, aux=z, ldaux=I, epi=EPI_GELU)
+        y = fmt.empty(M, N, dev)
+        fmt.gemm(h, I, 0, *fmt.weight(w2), 1, y, N, M, N, I, bias=b2)
         ctx.dims, ctx.lda, ctx.in_shape = (M, K, I, N), lda, x.shape
         ctx.targets = (_targets_of(w1), _targets_of(w2), _targets_of(b1), _targets_of(b2))
         ctx.save_for_backward(x2, w1, w2, z, None if ctx.recompute_h else h)
@@ -707,50 +796,53 @@ class FFNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dres=None):
-        tail = (None,) * (len(ctx.needs_input_grad) - 5)          # passthrough / recompute_h: as many as the call passed
+        tail = (None,) * (len(ctx.needs_input_grad) - 5)          # passthrough / recompute_h / fmt: as many as the call passed
         if dy is None:
             return ((dres if ctx.needs_input_grad[0] else None), None, None, None, None) + tail
+        fmt = ctx.fmt
         x2, w1, w2, z, h = ctx.saved_tensors
         M, K, I, N = ctx.dims
-        dy = dy.reshape(M, N)
-        if not dy.is_contiguous():
-            dy = dy.contiguous()
+        dy_in = dy
+        dy, ldy, _ = fmt.grad_rows(dy, M, N)
         dev = dy.device
-        dz = torch.empty((M, I), dtype=torch.float32, device=dev)
+        dz = fmt.empty(M, I, dev)
         db2 = _direct_grad(ctx.targets[3], (N,))
         if db2 is None:
             db2 = torch.empty(N, dtype=torch.float32, device=dev)
         db1 = _direct_grad(ctx.targets[2], (I,))
         if db1 is None:
             db1 = torch.empty(I, dtype=torch.float32, device=dev)
-        _gemm(dy, N, 0, w2, w2.stride(0), 0, dz, I, M, I, N, aux=z, ldaux=I, epi=EPI_MUL_DGELU)   # dH * gelu'(z)
+        fmt.gemm(dy, ldy, 0, *fmt.weight(w2), 0, dz, I, M, I, N, aux=z, ldaux=I, epi=EPI_MUL_DGELU)   # dH * gelu'(z)
         dw2 = _direct_grad(ctx.targets[1], (N, I))
         if dw2 is None:
             dw2 = torch.empty((N, I), dtype=torch.float32, device=dev)
         if h is None:          # recompute_h: h = gelu(z), alive for the one GEMM that reads it
-            h = torch.empty((M, I), dtype=torch.float32, device=dev)
+            h = fmt.empty(M, I, dev)
             call("ytvln_gelu_fwd_f32", _ptr(z), _ptr(h), M * I, _stream())
-        db2_done = _gemm(dy, N, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2)          # db2 rides on the dW2 GEMM
+        db2_done = fmt.gemm(dy, ldy, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2)          # db2 rides on the dW2 GEMM
         del h
         if not db2_done:
-            colsum(dy, M, N, N, out=db2)
+            d32, ld32 = fmt.f32_rows(dy, ldy, N)
+            colsum(d32, M, N, ld32, out=db2)
         dx = None
         if ctx.needs_input_grad[0]:
-            acc = _accumulate_target(dres, M, K, dy)      # (dy is consumed by now, but it may be retained / hooked upstream)
+            w, ldw = fmt.weight(w1)
+            acc = fmt.accumulate_target(dres, M, K, dy, dy_in)      # (dy is consumed by now, but it may be retained / hooked upstream)
             if acc is not None:          # the residual around the FFN: accumulate into its gradient (see LinearFn)
-                _gemm(dz, I, 0, w1, w1.stride(0), 0, acc, K, M, K, I, beta=1.0)
+                fmt.gemm(dz, I, 0, w, ldw, 0, acc, K, M, K, I, beta=1.0)
                 dx = acc.view(ctx.in_shape)
             else:
-                dx = torch.empty((M, K), dtype=torch.float32, device=dev)
-                _gemm(dz, I, 0, w1, w1.stride(0), 0, dx, K, M, K, I)
+                dx = fmt.empty(M, K, dev)
+                fmt.gemm(dz, I, 0, w, ldw, 0, dx, K, M, K, I)
                 dx = dx.view(ctx.in_shape)
                 if dres is not None:
                     dx = dx + dres.reshape(ctx.in_shape)
         dw1 = _direct_grad(ctx.targets[0], (I, K))
         if dw1 is None:
             dw1 = torch.empty((I, K), dtype=torch.float32, device=dev)
-        if not _gemm(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1):
-            colsum(dz, M, I, I, out=db1)
+        if not fmt.gemm(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1):
+            d32, ld32 = fmt.f32_rows(dz, I, I)
+            colsum(d32, M, I, ld32, out=db1)
         return (dx, dw1, db1, dw2, db2) + tail
 
 
@@ -759,27 +851,21 @@ _NO_BF16_RECOMPUTE_H = ('recompute = "ffn" with bf16 hidden states: the bf16-res
                         'path) or "none"')
 
 
+def _ffn(x, w1, b1, w2, b2, passthrough: bool, recompute_h: bool):
+    fmt = _format_of(x)
+    if recompute_h and not fmt.exact_gelu_replay:
+        raise NotImplementedError(_NO_BF16_RECOMPUTE_H)
+    return FFNFn.apply(x, w1, b1, w2, b2, passthrough, recompute_h, fmt)
+
+
 def ffn(x, w1, b1, w2, b2, recompute_h: bool = False) -> Tensor:
     """`recompute_h`: see FFNFn (fp32 hidden states only; bf16 ones are refused)."""
-    if x.dtype == torch.bfloat16:
-        if recompute_h:
-            raise NotImplementedError(_NO_BF16_RECOMPUTE_H)
-        return FFNBf16Fn.apply(x, w1, b1, w2, b2)
-    if recompute_h:
-        return FFNFn.apply(x, w1, b1, w2, b2, False, True)
-    return FFNFn.apply(x, w1, b1, w2, b2)
+    return _ffn(x, w1, b1, w2, b2, False, recompute_h)
 
 
 def ffn_res(x, w1, b1, w2, b2, recompute_h: bool = False) -> Tuple[Tensor, Tensor]:
     """(ffn(x, ...), x) -- the second value feeds the residual add behind the FFN (see LinearFn)."""
-    if x.dtype == torch.bfloat16:
-        if recompute_h:
-            raise NotImplementedError(_NO_BF16_RECOMPUTE_H)
-        return FFNBf16Fn.apply(x, w1, b1, w2, b2, True)
-    if recompute_h:
-        return FFNFn.apply(x, w1, b1, w2, b2, True, True)
-    return FFNFn.apply(x, w1, b1, w2, b2, True)
-
+    return _ffn(x, w1, b1, w2, b2, True, recompute_h)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -863,291 +949,47 @@ def _gemm_bf16(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=N
     return bool(done.value)
 
 
-def _rows2d_bf16(x: Tensor) -> Tuple[Tensor, int, int, int]:
-    """View a bf16 tensor as [M, K] rows with unit inner stride and a leading dimension that is a multiple of 8."""
-    K = x.shape[-1]
-    if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0:
-        return x, x.shape[0], K, x.stride(0)
-    if not x.is_contiguous():
-        x = x.contiguous()
-    return x, x.numel() // max(K, 1), K, K
-
-
-def _grad_rows_bf16(dy: Tensor, M: int, N: int):
-    """(dy as bf16 [M, N] rows, leading dimension, GEMM flags).  bf16 gradients with a padded leading dimension come from the loss kernels
-    (ytvln_ce_bwd_bf16 / ytvln_kl_bwd_bf16: zero padding written by the kernel) and are used in place; fp32 gradients (the small heads on the
-    pooled vectors) are cast; anything unaligned is repacked into a zero-padded buffer."""
-    if dy.dtype == torch.float32:
-        dy = cast_bf16(dy.reshape(M, N))
-    d2 = dy.reshape(M, N)
-    if d2.stride(1) == 1 and d2.stride(0) % 8 == 0 and d2.data_ptr() % 16 == 0 and (d2.stride(0) == N or
-                                                                                   _ZERO_PADDED.get(d2.untyped_storage().data_ptr()) == d2.stride(0)):
-        return d2, d2.stride(0), (GEMM_A_ZERO_PADDED if d2.stride(0) != N else 0)
-    ld = _pad8(N)
-    if ld == N:
-        return d2.contiguous(), N, 0
-    full = torch.zeros((M, ld), dtype=_BF16, device=dy.device)
-    full[:, :N].copy_(d2)
-    return full[:, :N], ld, GEMM_A_ZERO_PADDED
-
-
-def _alloc_rows_bf16(M: int, N: int, device):
-    """[M, N] bf16 view with leading dimension _pad8(N); the caller's kernel writes zeros into the padding (and that is remembered)."""
-    ld = _pad8(N)
-    if ld == N:
-        return torch.empty((M, N), dtype=_BF16, device=device), N
-    full = torch.empty((M, ld), dtype=_BF16, device=device)
-    key = full.untyped_storage().data_ptr()
-    _ZERO_PADDED[key] = ld
-    _weakref.finalize(full, _ZERO_PADDED.pop, key, None)
-    return full[:, :N], ld
-
-
-class LinearBf16Fn(torch.autograd.Function):
-    """y = act(x W^T + b) on the bf16-resident path (same contract as LinearFn, incl. `passthrough`).  x: bf16 hidden states (or fp32 network
-    inputs, cast once); W: the bf16 copy of the fp32 master weight; y: bf16, or fp32 when `out_fp32` (pooled vectors).  Backward:
-    dX = dY W and dW = dY^T X read dY, W and X as they lie in HBM (k-major operands through the transposing LDS read); dW and db are fp32
-    and go straight into the gradient arena; db rides on the dW launch."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, act, passthrough=False, out_fp32=False):
-        ctx.set_materialize_grads(False)
-        ctx.passthrough = bool(passthrough)
-        ctx.x_was_f32 = x.dtype == torch.float32
-        xb = cast_bf16(x) if ctx.x_was_f32 else x
-        _check(xb, "x", _BF16)
-        x2, M, K, lda = _rows2d_bf16(xb)
-        _check(weight, "weight")
-        N = weight.shape[0]
-        assert weight.shape[1] == K, (weight.shape, K)
-        wb = _bf16_weight(weight)
-        need_grad = any(ctx.needs_input_grad)
-        epi = _ACT[act]
-        if epi == ACT_SWISH:          # unfused, as in LinearFn: z is bf16 like the gelu aux
-            z, ldy = torch.empty((M, N), dtype=_BF16, device=x.device), N
-            _gemm_bf16(x2, lda, 0, wb, K, 1, z, N, M, N, K, bias=bias)
-            y = torch.empty_like(z) if need_grad else z
-            call("ytvln_act_fwd_bf16", z.data_ptr(), y.data_ptr(), M * N, ACT_SWISH, _stream())
-            if out_fp32:
-                y = y.float()
-        else:
-            if out_fp32:
-                y, ldy = _alloc_rows(M, N, x.device)
-            else:
-                y, ldy = torch.empty((M, N), dtype=_BF16, device=x.device), N
-            z = torch.empty((M, N), dtype=_BF16, device=x.device) if (epi == EPI_GELU and need_grad) else None
-            _gemm_bf16(x2, lda, 0, wb, K, 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
-        ctx.epi, ctx.dims, ctx.lda, ctx.has_bias = epi, (M, N, K), lda, bias is not None
-        ctx.in_shape = x.shape
-        ctx.targets = _targets_of(weight)
-        ctx.btargets = _targets_of(bias) if bias is not None else None
-        # the ReLU backward needs the sign of the OUTPUT: a bf16 copy of it when the output itself leaves as fp32
-        aux = z if epi in (EPI_GELU, ACT_SWISH) else ((y if y.dtype == _BF16 else cast_bf16(y)) if (epi == EPI_RELU and need_grad) else None)
-        ctx.save_for_backward(x2, weight, aux)
-        out = _view_rows_as(y, ldy, tuple(x.shape[:-1]) + (N,))
-        return (out, x) if ctx.passthrough else out
-
-    @staticmethod
-    def backward(ctx, dy, dres=None):
-        if dy is None:
-            return (dres if ctx.needs_input_grad[0] else None), None, None, None, None, None
-        x2, weight, aux = ctx.saved_tensors
-        M, N, K = ctx.dims
-        dy, ldy, flags = _grad_rows_bf16(dy, M, N)
-        if ctx.epi != EPI_NONE:
-            if ldy != N:
-                dy, ldy, flags = dy.contiguous(), N, 0
-            dz = torch.empty((M, N), dtype=_BF16, device=dy.device)
-            call("ytvln_act_bwd_bf16", dy.data_ptr(), aux.data_ptr(), dz.data_ptr(), dy.numel(), ctx.epi, _stream())
-            dy = dz
-        dx = dw = db = None
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if want_db:
-            db = _direct_grad(ctx.btargets, (N,))
-            if db is None:
-                db = torch.empty(N, dtype=torch.float32, device=dy.device)
-        if ctx.needs_input_grad[0]:
-            wb = _bf16_weight(weight)
-            acc = None
-            if not ctx.x_was_f32 and dres is not None and dres.dtype == _BF16 and dres.is_contiguous() and dres.numel() == M * K and \
-                    not _overlaps(dres, dy):
-                acc = dres.view(M, K)
-            if acc is not None:          # dx = d(residual) + dY W, accumulated over the residual branch's gradient (beta = 1)
-                _gemm_bf16(dy, ldy, 0, wb, K, 0, acc, K, M, K, N, beta=1.0, flags=flags)
-                dx = acc.view(ctx.in_shape)
-            else:
-                dx = torch.empty((M, K), dtype=_BF16, device=dy.device)
-                _gemm_bf16(dy, ldy, 0, wb, K, 0, dx, K, M, K, N, flags=flags)
-                dx = dx.view(ctx.in_shape)
-                if dres is not None:
-                    dx = dx + dres.reshape(ctx.in_shape)
-                if ctx.x_was_f32:
-                    dx = dx.float()
-        db_done = False
-        if ctx.needs_input_grad[1]:
-            dw = _direct_grad(ctx.targets, (N, K))
-            if dw is None:
-                dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
-            # dW[N, K] = dY^T X: both operands k-major (the contraction index M is their row); db = row sums of dY^T ride on the launch
-            db_done = _gemm_bf16(dy, ldy, 1, x2, ctx.lda, 0, dw, K, N, K, M, flags=flags, rowsum=db if want_db else None)
-        if want_db and not db_done:
-            colsum(dy.float() if ldy == N else dy.contiguous().float(), M, N, N, out=db)
-        return dx, dw, db, None, None, None
-
-
-class FFNBf16Fn(torch.autograd.Function):
-    """out = gelu(x W1^T + b1) W2^T + b2 on the bf16-resident path (BertIntermediate + BertOutput.dense, vilbert.py:351-354, 365): x, the
-    GELU pre-activation z, the hidden h and out are bf16; the backward fuses GELU' into the epilogue of the dX GEMM of the second projection."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, passthrough=False):
-        ctx.set_materialize_grads(False)
-        ctx.passthrough = bool(passthrough)
-        _check(x, "x", _BF16)
-        x2, M, K, lda = _rows2d_bf16(x)
-        I, N = w1.shape[0], w2.shape[0]
-        need_grad = any(ctx.needs_input_grad)
-        dev = x.device
-        h = torch.empty((M, I), dtype=_BF16, device=dev)
-        z = torch.empty((M, I), dtype=_BF16, device=dev) if need_grad else None
-        _gemm_bf16(x2, lda, 0, _bf16_weight(w1), K, 1, h, I, M, I, K, bias=b1, aux=z, ldaux=I, epi=EPI_GELU)
-        y = torch.empty((M, N), dtype=_BF16, device=dev)
-        _gemm_bf16(h, I, 0, _bf16_weight(w2), I, 1, y, N, M, N, I, bias=b2)
-        ctx.dims, ctx.lda, ctx.in_shape = (M, K, I, N), lda, x.shape
-        ctx.targets = (_targets_of(w1), _targets_of(w2), _targets_of(b1), _targets_of(b2))
-        ctx.save_for_backward(x2, w1, w2, z, h)
-        out = y.view(*x.shape[:-1], N)
-        return (out, x) if ctx.passthrough else out
-
-    @staticmethod
-    def backward(ctx, dy, dres=None):
-        if dy is None:
-            return (dres if ctx.needs_input_grad[0] else None), None, None, None, None, None
-        x2, w1, w2, z, h = ctx.saved_tensors
-        M, K, I, N = ctx.dims
-        dy, ldy, _ = _grad_rows_bf16(dy, M, N)
-        dev = dy.device
-        dz = torch.empty((M, I), dtype=_BF16, device=dev)
-        db2 = _direct_grad(ctx.targets[3], (N,))
-        if db2 is None:
-            db2 = torch.empty(N, dtype=torch.float32, device=dev)
-        db1 = _direct_grad(ctx.targets[2], (I,))
-        if db1 is None:
-            db1 = torch.empty(I, dtype=torch.float32, device=dev)
-        _gemm_bf16(dy, ldy, 0, _bf16_weight(w2), I, 0, dz, I, M, I, N, aux=z, ldaux=I, epi=EPI_MUL_DGELU)   # dH * gelu'(z)
-        dw2 = _direct_grad(ctx.targets[1], (N, I))
-        if dw2 is None:
-            dw2 = torch.empty((N, I), dtype=torch.float32, device=dev)
-        if not _gemm_bf16(dy, ldy, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2):
-            colsum(dy.float(), M, N, N, out=db2)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            acc = None
-            if dres is not None and dres.dtype == _BF16 and dres.is_contiguous() and dres.numel() == M * K and not _overlaps(dres, dy):
-                acc = dres.view(M, K)
-            if acc is not None:          # the residual around the FFN: accumulate into its gradient
-                _gemm_bf16(dz, I, 0, _bf16_weight(w1), K, 0, acc, K, M, K, I, beta=1.0)
-                dx = acc.view(ctx.in_shape)
-            else:
-                dx = torch.empty((M, K), dtype=_BF16, device=dev)
-                _gemm_bf16(dz, I, 0, _bf16_weight(w1), K, 0, dx, K, M, K, I)
-                dx = dx.view(ctx.in_shape)
-                if dres is not None:
-                    dx = dx + dres.reshape(ctx.in_shape)
-        dw1 = _direct_grad(ctx.targets[0], (I, K))
-        if dw1 is None:
-            dw1 = torch.empty((I, K), dtype=torch.float32, device=dev)
-        if not _gemm_bf16(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1):
-            colsum(dz.float(), M, I, I, out=db1)
-        return dx, dw1, db1, dw2, db2, None
-
-
-def _ln_bwd_bf16(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, gb_targets=None, want_bf16=True, want_f32=False):
-    """-> (ds bf16 | None, dx bf16 (= ds when p_pre == 0), ds fp32 | None, dgamma, dbeta)."""
-    if dy.dtype != _BF16:
-        dy = cast_bf16(dy.reshape(rows, H))
-    dy = dy.reshape(rows, H)
-    if not dy.is_contiguous():
-        dy = dy.contiguous()
-    ds = torch.empty((rows, H), dtype=_BF16, device=dy.device) if want_bf16 else None
-    dx = torch.empty((rows, H), dtype=_BF16, device=dy.device) if p_pre > 0 else None
-    ds32 = torch.empty((rows, H), dtype=torch.float32, device=dy.device) if want_f32 else None
-    nb = _lib.load().ytvln_ln_bwd_blocks(rows)
-    partial = torch.empty((nb, 2 * H), dtype=torch.float32, device=dy.device)
-    call("ytvln_ln_bwd_bf16", dy.data_ptr(), s.data_ptr(), _ptr(mean), _ptr(rstd), _ptr(gamma), ds.data_ptr() if ds is not None else None,
-         dx.data_ptr() if dx is not None else None, _ptr(ds32), _ptr(partial), rows, H, float(p_pre), float(p_post),
-         _ptr(rng) if rng is not None else None, int(site), _stream())
-    gb = colsum(partial, nb, 2 * H, 2 * H, out=_direct_grad(gb_targets, (2 * H,)))
-    return ds, (dx if dx is not None else ds), ds32, gb[:H], gb[H:]
-
-
-class AddLayerNormBf16Fn(torch.autograd.Function):
-    """y = LN(dropout(x) + residual) on bf16 rows (statistics, gamma / beta and their gradients fp32); saves s = dropout(x) + residual as bf16."""
-
-    @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps, p_pre, p_post, rng, site):
-        ctx.set_materialize_grads(False)
-        _check(x, "x", _BF16)
-        H = x.shape[-1]
-        xc = x if x.is_contiguous() else x.contiguous()
-        rc = None
-        if res is not None:
-            _check(res, "residual", _BF16)
-            rc = res if res.is_contiguous() else res.contiguous()
-        rows = xc.numel() // H
-        need_grad = any(ctx.needs_input_grad)
-        y = torch.empty_like(xc)
-        s = torch.empty_like(xc) if need_grad else None
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device) if need_grad else None
-        rstd = torch.empty_like(mean) if need_grad else None
-        call("ytvln_ln_fwd_bf16", xc.data_ptr(), rc.data_ptr() if rc is not None else None, _ptr(gamma), _ptr(beta), y.data_ptr(),
-             s.data_ptr() if s is not None else None, _ptr(mean), _ptr(rstd), rows, H, float(eps), float(p_pre), float(p_post),
-             _ptr(rng) if rng is not None else None, int(site), _stream())
-        ctx.meta = (rows, H, p_pre, p_post, site, res is not None)
-        ctx.gb = (gamma, beta) if isinstance(gamma, torch.nn.Parameter) and isinstance(beta, torch.nn.Parameter) else None
-        ctx.save_for_backward(s, mean, rstd, gamma, rng)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        if dy is None:
-            return (None,) * 9
-        s, mean, rstd, gamma, rng = ctx.saved_tensors
-        rows, H, p_pre, p_post, site, has_res = ctx.meta
-        ds, dx, _, dg, db = _ln_bwd_bf16(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, ctx.gb)
-        shape = dy.shape
-        return (dx.view(shape) if ctx.needs_input_grad[0] else None,
-                ds.view(shape) if (has_res and ctx.needs_input_grad[1]) else None, dg, db, None, None, None, None, None)
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # LayerNorm family
 # ------------------------------------------------------------------------------------------------------------------
-def _ln_bwd(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, gb_targets=None):
-    dy = dy.reshape(rows, H)
+def _ln_bwd(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, gb_targets=None, fmt=_F32, want_rows=True, want_f32=False):
+    """-> (ds, dx (= ds when p_pre == 0), dgamma, dbeta), ds / dx rows of `fmt`; statistics, gamma / beta and their gradients fp32.
+    `want_f32` (the embedding-table gradient kernels read fp32 rows) -> (ds | None, dx, ds as fp32 rows, dgamma, dbeta): fp32 rows serve as they
+    are, bf16 rows get an fp32 copy written by the same launch, and the bf16 ds itself only with `want_rows`."""
+    dy = fmt.cast(dy.reshape(rows, H)).reshape(rows, H)
     if not dy.is_contiguous():
         dy = dy.contiguous()
-    ds = torch.empty((rows, H), dtype=torch.float32, device=dy.device)
-    dx = torch.empty_like(ds) if p_pre > 0 else None
+    dev = dy.device
+    copy32 = want_f32 and fmt.ln_bwd_f32_copy
+    ds = fmt.empty(rows, H, dev) if (want_rows or not copy32) else None
+    dx = fmt.empty(rows, H, dev) if p_pre > 0 else None
+    ds32 = torch.empty((rows, H), dtype=torch.float32, device=dev) if copy32 else None
     nb = _lib.load().ytvln_ln_bwd_blocks(rows)
-    partial = torch.empty((nb, 2 * H), dtype=torch.float32, device=dy.device)
-    call("ytvln_ln_bwd_f32", _ptr(dy), _ptr(s), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(ds), _ptr(dx), _ptr(partial), rows, H,
-         float(p_pre), float(p_post), _ptr(rng) if rng is not None else None, int(site), _stream())
+    partial = torch.empty((nb, 2 * H), dtype=torch.float32, device=dev)
+    call("ytvln_ln_bwd_" + fmt.suffix, _ptr(dy), _ptr(s), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(ds), _ptr(dx),
+         *((_ptr(ds32),) if fmt.ln_bwd_f32_copy else ()), _ptr(partial), rows, H, float(p_pre), float(p_post),
+         _ptr(rng) if rng is not None else None, int(site), _stream())
     gb = colsum(partial, nb, 2 * H, 2 * H, out=_direct_grad(gb_targets, (2 * H,)))      # LayerNorm.weight | LayerNorm.bias
-    return ds, (dx if dx is not None else ds), gb[:H], gb[H:]
+    dx = dx if dx is not None else ds
+    if want_f32:
+        return ds, dx, (ds32 if copy32 else ds), gb[:H], gb[H:]
+    return ds, dx, gb[:H], gb[H:]
 
 
 class AddLayerNormFn(torch.autograd.Function):
-    """y = LN(dropout(x) + residual) [dropout after] -- BertLayerNorm with its surrounding dropout / residual add."""
+    """y = LN(dropout(x) + residual) [dropout after] -- BertLayerNorm with its surrounding dropout / residual add, on rows of `fmt` (statistics,
+    gamma / beta and their gradients fp32); saves s = dropout(x) + residual in that format."""
 
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps, p_pre, p_post, rng, site):
+    def forward(ctx, x, res, gamma, beta, eps, p_pre, p_post, rng, site, fmt=_F32):
         ctx.set_materialize_grads(False)
-        _check(x, "x")
+        ctx.fmt = fmt
+        _check(x, "x", fmt.dtype)
         H = x.shape[-1]
         xc = x if x.is_contiguous() else x.contiguous()
         rc = None
         if res is not None:
+            _check(res, "residual", fmt.dtype)
             rc = res if res.is_contiguous() else res.contiguous()
         rows = xc.numel() // H
         need_grad = any(ctx.needs_input_grad)
@@ -1155,7 +997,7 @@ class AddLayerNormFn(torch.autograd.Function):
         s = torch.empty_like(xc) if need_grad else None
         mean = torch.empty(rows, dtype=torch.float32, device=x.device) if need_grad else None
         rstd = torch.empty_like(mean) if need_grad else None
-        call("ytvln_ln_fwd_f32", _ptr(xc), _ptr(rc), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(s), _ptr(mean), _ptr(rstd), rows, H,
+        call("ytvln_ln_fwd_" + fmt.suffix, _ptr(xc), _ptr(rc), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(s), _ptr(mean), _ptr(rstd), rows, H,
              float(eps), float(p_pre), float(p_post), _ptr(rng) if rng is not None else None, int(site), _stream())
         ctx.meta = (rows, H, p_pre, p_post, site, res is not None)
         ctx.gb = (gamma, beta) if isinstance(gamma, torch.nn.Parameter) and isinstance(beta, torch.nn.Parameter) else None
@@ -1164,23 +1006,23 @@ class AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        tail = (None,) * (len(ctx.needs_input_grad) - 4)
         if dy is None:
-            return (None,) * 9
+            return (None,) * 4 + tail
         s, mean, rstd, gamma, rng = ctx.saved_tensors
         rows, H, p_pre, p_post, site, has_res = ctx.meta
-        ds, dx, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, ctx.gb)
+        ds, dx, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, ctx.gb, ctx.fmt)
         shape = dy.shape
         return (dx.view(shape) if ctx.needs_input_grad[0] else None,
-                ds.view(shape) if (has_res and ctx.needs_input_grad[1]) else None, dg, db, None, None, None, None, None)
+                ds.view(shape) if (has_res and ctx.needs_input_grad[1]) else None, dg, db) + tail
 
 
 def add_layer_norm(x, res, gamma, beta, eps=1e-12, p_pre=0.0, p_post=0.0, drop: Optional[DropoutState] = None) -> Tensor:
     if (p_pre > 0 or p_post > 0) and drop is None:
         raise RuntimeError("dropout requested without a DropoutState")
     use = drop is not None and (p_pre > 0 or p_post > 0)
-    fn = AddLayerNormBf16Fn if x.dtype == torch.bfloat16 else AddLayerNormFn
-    return fn.apply(x, res, gamma, beta, eps, p_pre if use else 0.0, p_post if use else 0.0,
-                    drop.tensor if use else None, drop.next_site() if use else 0)
+    return AddLayerNormFn.apply(x, res, gamma, beta, eps, p_pre if use else 0.0, p_post if use else 0.0,
+                                drop.tensor if use else None, drop.next_site() if use else 0, _format_of(x))
 
 
 class TextEmbedFn(torch.autograd.Function):
@@ -1216,10 +1058,8 @@ class TextEmbedFn(torch.autograd.Function):
         ids, tt, s, mean, rstd, gamma, rng = ctx.saved_tensors
         N, T, H, p_post, site, wshape, pshape, tshape = ctx.meta
         rows = N * T
-        if s.dtype == torch.bfloat16:          # bf16-resident path: the table-gradient kernels below read an fp32 copy of ds
-            _, _, ds, dg, db = _ln_bwd_bf16(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site, want_bf16=False, want_f32=True)
-        else:
-            ds, _, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site)
+        # the table-gradient kernels below read fp32 rows of ds (bf16-resident path: an fp32 copy, and no bf16 ds: nothing reads it)
+        _, _, ds, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site, fmt=_format_of(s), want_rows=False, want_f32=True)
         dev = ds.device
         dword = torch.zeros(wshape, dtype=torch.float32, device=dev)
         # token ids repeat inside a batch: sorted (stable) so that one wave owns each id's run -- no atomics, reproducible sums
@@ -1294,17 +1134,14 @@ class ImageEmbedFn(torch.autograd.Function):
             return (None,) * 15
         locc, s, mean, rstd, gamma, rng = ctx.saved_tensors
         rows, H, p_post, site, KT = ctx.meta
-        dimg = None
-        if s.dtype == torch.bfloat16:          # bf16-resident path: bf16 ds for the feature projection's backward, an fp32 copy for the small kernels below
-            dimg, _, ds, dg, db = _ln_bwd_bf16(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site, want_bf16=True, want_f32=True)
-        else:
-            ds, _, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site)
+        # ds in img's format for the feature projection's backward, as fp32 rows for the small kernels below (fp32 path: one and the same buffer)
+        dimg, _, ds, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site, fmt=_format_of(s), want_f32=True)
         dev = ds.device
         dwall = torch.empty((H, 12), dtype=torch.float32, device=dev)
         _gemm(ds, H, 1, locc, 12, 0, dwall, 12, H, 12, rows)               # ds^T . loc  -> [H, 12]
         dbias = colsum(ds, rows, H, H)
         dE = colsum_by_index(ds, rows, H, H, KT, idx_f32=locc, idx_stride=12, idx_f32_offset=11)
-        return ((dimg if dimg is not None else ds).view(dy.shape), None, dwall[:, 0:5].contiguous(), dbias, dwall[:, 5:9].contiguous(), dbias,
+        return (dimg.view(dy.shape), None, dwall[:, 0:5].contiguous(), dbias, dwall[:, 5:9].contiguous(), dbias,
                 dwall[:, 9:11].contiguous(), dbias, dE, dg, db, None, None, None, None)
 
 
@@ -1326,7 +1163,7 @@ class GatherRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, idx):
         ctx.set_materialize_grads(False)
-        x2, M, H, ld = _rows2d(x, "x")
+        x2, M, H, ld = _F32.rows(x, "x")
         idx = _i64(idx, "idx").reshape(-1)
         out = torch.empty((idx.numel(), H), dtype=torch.float32, device=x.device)
         call("ytvln_gather_rows_f32", _ptr(x2), ld, _ptr(idx), idx.numel(), H, _ptr(out), _stream())
@@ -1446,7 +1283,7 @@ class RowLogitFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise RuntimeError(f"ytvln.ops.row_logit: `x` must be float32 or bfloat16; got {x.dtype}")
-        x2, rows, H, ldx = _rows2d_any(x)
+        x2, rows, H, ldx = _format_of(x).rows(x, "x")
         _check(weight, "weight")
         if weight.numel() != H:
             raise RuntimeError(f"ytvln.ops.row_logit: weight of {weight.numel()} elements for rows of {H}")
@@ -1825,7 +1662,7 @@ class CrossEntropyFn(torch.autograd.Function):
     def forward(ctx, logits, target, ignore_index):
         ctx.set_materialize_grads(False)
         bf = logits.dtype == _BF16             # bf16-resident path: bf16 logits in, bf16 gradient out (same kernels, 2-byte loads/stores)
-        lg, M, V, ld = _rows2d_any(logits) if bf else _rows2d(logits, "logits")
+        lg, M, V, ld = _format_of(logits).rows(logits, "logits")
         tg = _i64(target, "target").reshape(-1)
         assert tg.numel() == M, (tg.shape, M)
         dev = lg.device
@@ -1850,7 +1687,7 @@ class CrossEntropyFn(torch.autograd.Function):
             dl, ldd = _alloc_rows_bf16(M, V, lg.device)
             call("ytvln_ce_bwd_bf16", lg.data_ptr(), ld, _ptr(tg), ign, _ptr(row_lse), _ptr(out), _ptr(g), dl.data_ptr(), ldd, M, V, _stream())
             return _view_rows_as(dl, ldd, shape), None, None
-        dl, ldd = _alloc_rows(M, V, lg.device, zero_pad=True)
+        dl, ldd = _F32.alloc_rows(M, V, lg.device, zero_pad=True)
         call("ytvln_ce_bwd_f32", _ptr(lg), ld, _ptr(tg), ign, _ptr(row_lse), _ptr(out), _ptr(g), _ptr(dl), ldd, M, V, _stream())
         return _view_rows_as(dl, ldd, shape), None, None
 
@@ -1866,8 +1703,8 @@ class KLMaskedFn(torch.autograd.Function):
     def forward(ctx, pred, target, mask):
         ctx.set_materialize_grads(False)
         bf = pred.dtype == _BF16
-        pr, M, Cc, ld = _rows2d_any(pred) if bf else _rows2d(pred, "pred")
-        tg, M2, C2, ldt = _rows2d(target, "target")
+        pr, M, Cc, ld = _format_of(pred).rows(pred, "pred")
+        tg, M2, C2, ldt = _F32.rows(target, "target")
         assert (M, Cc) == (M2, C2), (pred.shape, target.shape)
         mk = _i64(mask, "mask").reshape(-1)
         dev = pr.device
@@ -1892,7 +1729,7 @@ class KLMaskedFn(torch.autograd.Function):
             dp, ldd = _alloc_rows_bf16(M, Cc, pr.device)
             call("ytvln_kl_bwd_bf16", pr.data_ptr(), ld, _ptr(tg), ldt, _ptr(mk), _ptr(row_lse), _ptr(out), _ptr(g), dp.data_ptr(), ldd, M, Cc, _stream())
             return _view_rows_as(dp, ldd, shape), None, None
-        dp, ldd = _alloc_rows(M, Cc, pr.device, zero_pad=True)
+        dp, ldd = _F32.alloc_rows(M, Cc, pr.device, zero_pad=True)
         call("ytvln_kl_bwd_f32", _ptr(pr), ld, _ptr(tg), ldt, _ptr(mk), _ptr(row_lse), _ptr(out), _ptr(g), _ptr(dp), ldd, M, Cc, _stream())
         return _view_rows_as(dp, ldd, shape), None, None
 
@@ -1938,10 +1775,10 @@ class BCERowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t, pos_weight, scale):
         ctx.set_materialize_grads(False)
-        x2, M, Cc, ldx = _rows2d(x, "x")
+        x2, M, Cc, ldx = _F32.rows(x, "x")
         if not t.is_cuda:
             raise RuntimeError(f"ytvln.ops: `t` must live on the GPU (no CPU fallback); got device {t.device}")
-        t2, M2, C2, ldt = _rows2d(t if t.dtype == torch.float32 else t.to(torch.float32), "t")
+        t2, M2, C2, ldt = _F32.rows(t if t.dtype == torch.float32 else t.to(torch.float32), "t")
         if (M, Cc) != (M2, C2):
             raise RuntimeError(f"ytvln.ops.bce_with_logits_rows: logits {tuple(x.shape)} against targets {tuple(t.shape)}")
         pw, pw_stride = None, 0
@@ -1971,7 +1808,7 @@ class BCERowsFn(torch.autograd.Function):
         x2, t2, pw = ctx.saved_tensors
         M, Cc, ldx, ldt, pw_stride, scale, shape = ctx.meta
         g = g.reshape(1).contiguous().float()
-        dx, lddx = _alloc_rows(M, Cc, x2.device, zero_pad=True)
+        dx, lddx = _F32.alloc_rows(M, Cc, x2.device, zero_pad=True)
         call("ytvln_bce_rows_bwd_f32", _ptr(x2), ldx, _ptr(t2), ldt, _ptr(pw), pw_stride, scale, _ptr(g), _ptr(dx), lddx, M, Cc, _stream())
         return _view_rows_as(dx, lddx, shape), None, None, None
 
