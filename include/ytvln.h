@@ -190,6 +190,22 @@ int ytvln_randomize_regions(float* features, int64_t ldf, const float* probs, co
  * ytvln_scatter_add_rows_f32 with skip_idx = -1. */
 int ytvln_gather_rows_f32(const float* x, int64_t ldx, const int64_t* idx, int R, int H, float* out, void* stream);
 
+/* Packed rows (csrc/rows.hip; BertModel.skip_padding): both streams of the model on the valid rows of a batch only.
+ *   ytvln_rows_plan: flags[rows] (one byte per padded row, non-zero = valid), 1 <= rows < 2^31, capacity >= 1 ->
+ *     pack_idx[capacity]  the padded row of each packed row: packed row j is the j-th flagged row in ascending order; -1 past the count;
+ *     unpack_idx[rows]    the packed row of each padded row: -1 for unflagged rows and for flagged rows that did not fit;
+ *     counts[0] = number of flagged rows, counts[1] = number of flagged rows that did not fit (max(counts[0] - capacity, 0)).
+ *     One launch of one workgroup, no atomics, no host sync, deterministic.
+ *   ytvln_rows_move_f32 / _bf16: out[j, 0:width] = 0 <= idx[j] < x_rows ? x[idx[j], 0:width] : 0 for j < out_rows; x and out have their own
+ *     leading dimensions (elements), a column window is the caller's pointer offset, columns of out past `width` are not touched.  width >= 1;
+ *     out_rows = 0 succeeds without a launch.  With pack_idx it packs (and is the backward of the unpack), with unpack_idx it unpacks (and
+ *     is the backward of the pack): the two index arrays of a plan describe one partial bijection. */
+int ytvln_rows_plan(const uint8_t* flags, int64_t rows, int64_t capacity, int64_t* pack_idx, int64_t* unpack_idx, int64_t* counts, void* stream);
+int ytvln_rows_move_f32(const float* x, int64_t ldx, int64_t x_rows, const int64_t* idx, int64_t out_rows, int width, float* out, int64_t ldo,
+                        void* stream);
+int ytvln_rows_move_bf16(const uint16_t* x, int64_t ldx, int64_t x_rows, const int64_t* idx, int64_t out_rows, int width, uint16_t* out,
+                         int64_t ldo, void* stream);
+
 /* Fused (dropout ->) residual add -> LayerNorm (-> dropout).  BertLayerNorm, vilbert.py:213-217 (biased variance, eps
  * inside the sqrt) together with the dropout/add that always precedes it (:322-324, :365-367, :641-648) or follows it
  * (:254-255, :1367-1368).

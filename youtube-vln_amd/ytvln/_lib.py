@@ -49,6 +49,10 @@ SIGNATURES = {
     "ytvln_scatter_add_rows_f32": [P, I64, P, I32, I32, P, I64, P],
     "ytvln_gather_rows_f32": [P, I64, P, I32, I32, P, P],
     "ytvln_scatter_add_rows_sorted_f32": [P, I64, P, P, I32, I32, P, I64, P],
+    # packed rows (csrc/rows.hip)
+    "ytvln_rows_plan": [P, I64, I64, P, P, P, P],
+    "ytvln_rows_move_f32": [P, I64, I64, P, I64, I32, P, I64, P],
+    "ytvln_rows_move_bf16": [P, I64, I64, P, I64, I32, P, I64, P],
     "ytvln_randomize_tokens": [P, P, I64, I32, I64, P, P, P, I64, P, P, P],
     "ytvln_randomize_regions": [P, I64, P, P, I64, I32, I32, P, P, I64, P, P, P],
     "ytvln_attn_keep_bytes": [I32, I32, I32, I32],

@@ -1195,6 +1195,90 @@ def select_rows(flag: Tensor, capacity: int) -> Tensor:
     return order[:capacity].contiguous()
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# packed rows (BertModel.skip_padding): the valid rows of a padded batch, moved by one kernel in all four directions
+# ------------------------------------------------------------------------------------------------------------------
+class RowsPlan:
+    """ytvln_rows_plan's outputs for one padding mask: `pack_idx` [capacity] (padded row of each packed row, -1 past the count), `unpack_idx`
+    [rows] (packed row of each padded row, -1 where there is none), `counts` [2] (flagged rows, flagged rows that did not fit) -- device int64
+    tensors -- and the two host integers `rows` and `capacity`."""
+    __slots__ = ("pack_idx", "unpack_idx", "counts", "rows", "capacity")
+
+    def __init__(self, pack_idx, unpack_idx, counts, rows, capacity):
+        self.pack_idx, self.unpack_idx, self.counts, self.rows, self.capacity = pack_idx, unpack_idx, counts, int(rows), int(capacity)
+
+    def record_stream(self, stream) -> None:
+        for t in (self.pack_idx, self.unpack_idx, self.counts):
+            t.record_stream(stream)
+
+
+def rows_capacity(rows: int, frac: float) -> int:
+    """Static capacity of a side: min(rows, ceil(frac * rows / 256) * 256) -- whole 256-row GEMM tiles, never more than the padded rows."""
+    return min(int(rows), int(math.ceil(float(frac) * int(rows) / 256.0)) * 256)
+
+
+def rows_plan(mask: Tensor, capacity: int) -> RowsPlan:
+    """Plan of the rows of `mask` (any shape; non-zero = valid) with room for `capacity` packed rows.  One launch, no host sync."""
+    if not mask.is_cuda:
+        raise RuntimeError(f"ytvln.ops: `mask` must live on the GPU (no CPU fallback); got device {mask.device}")
+    rows, capacity = mask.numel(), int(capacity)
+    flags = (mask.reshape(-1) != 0).contiguous()          # one byte per row
+    pack_idx = torch.empty(max(capacity, 0), dtype=torch.int64, device=mask.device)
+    unpack_idx = torch.empty(rows, dtype=torch.int64, device=mask.device)
+    counts = torch.empty(2, dtype=torch.int64, device=mask.device)
+    call("ytvln_rows_plan", flags.data_ptr(), rows, capacity, pack_idx.data_ptr(), unpack_idx.data_ptr(), counts.data_ptr(), _stream())
+    return RowsPlan(pack_idx, unpack_idx, counts, rows, capacity)
+
+
+def _rows_move(x2: Tensor, ld: int, x_rows: int, idx: Tensor, out_rows: int, width: int) -> Tensor:
+    out = torch.empty((out_rows, width), dtype=x2.dtype, device=x2.device)
+    call("ytvln_rows_move_bf16" if x2.dtype == torch.bfloat16 else "ytvln_rows_move_f32", x2.data_ptr(), ld, x_rows, idx.data_ptr(), out_rows, width,
+         out.data_ptr(), width, _stream())
+    return out
+
+
+class RowsMoveFn(torch.autograd.Function):
+    """out[j] = x[idx[j]] (zero rows where idx[j] < 0) over the rows of a [M, W] matrix, fp32 or bf16, read through (pointer, leading dimension).
+    `back_idx` is the other index array of the same plan: the backward is the same kernel with it."""
+
+    @staticmethod
+    def forward(ctx, x, idx, out_rows, back_idx):
+        ctx.set_materialize_grads(False)
+        _check(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
+        W = x.shape[-1]
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= W:
+            x2, ld = x, x.stride(0)          # a column window / padded leading dimension: read in place
+        else:
+            x2 = x.reshape(-1, W)
+            x2 = x2 if x2.is_contiguous() else x2.contiguous()
+            ld = W
+        M = x2.shape[0]
+        if back_idx.numel() != M or idx.numel() != out_rows:
+            raise RuntimeError(f"ytvln.ops: rows of x ({M}) / of the output ({out_rows}) do not match the plan ({back_idx.numel()}, {idx.numel()})")
+        ctx.meta = (M, W, x.shape)
+        ctx.save_for_backward(back_idx)
+        return _rows_move(x2, ld, M, idx, out_rows, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        (back_idx,) = ctx.saved_tensors
+        M, W, shape = ctx.meta
+        g = g if g.is_contiguous() else g.contiguous()
+        return _rows_move(g, W, g.shape[0], back_idx, M, W).view(shape), None, None, None
+
+
+def rows_pack(x: Tensor, plan: RowsPlan) -> Tensor:
+    """[capacity, W]: the valid rows of x (`plan.rows` rows of width W, any leading shape) in ascending order, zero rows past the count."""
+    return RowsMoveFn.apply(x, plan.pack_idx, plan.capacity, plan.unpack_idx)
+
+
+def rows_unpack(x: Tensor, plan: RowsPlan) -> Tensor:
+    """[rows, W]: packed rows back at their padded places, exact zeros everywhere else."""
+    return RowsMoveFn.apply(x, plan.unpack_idx, plan.rows, plan.pack_idx)
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, rng, site):

@@ -180,6 +180,16 @@ def _loss_aware_step(model, batch, args, all_options, capacity_frac):
     return outputs, losses, overflow
 
 
+def padding_row_overflow(model):
+    """Device scalar: valid rows that a static BertModel.skip_padding capacity has dropped so far (both sides, every forward of this model), or
+    None when the model does not run with skip_padding."""
+    for m in (model, getattr(model, "module", None)):
+        bert = getattr(m, "bert", None)
+        if bert is not None and getattr(bert, "skip_padding", None) is not None and getattr(bert, "padding_overflow", None) is not None:
+            return bert.padding_overflow.sum().float()
+    return None
+
+
 def train_step(model, optimizer, scheduler, batch, args, step: int = 0, logger=None, all_options=None,
                loss_aware_heads: bool = False, capacity_frac: float = 0.25, optimizer_step: bool = True, backward=None):
     """One iteration of train_epoch's body (utils_init.py:199-239): forward, loss composition in the reference's order,
@@ -194,6 +204,9 @@ def train_step(model, optimizer, scheduler, batch, args, step: int = 0, logger=N
         reduced_metrics["head_row_overflow"] = overflow        # device scalar; > 0 means capacity_frac was too small
     else:
         outputs = model(*get_model_input(batch, all_options))
+    dropped = padding_row_overflow(model)
+    if dropped is not None:
+        reduced_metrics["padding_row_overflow"] = dropped        # device scalar; > 0 means a skip_padding capacity was too small
     loss = None
     for task, flag in TASKS:
         if getattr(args, flag):
@@ -249,6 +262,9 @@ def train_epoch(epoch, model, optimizer, scheduler, data_loader, writer, default
                 # loss-aware heads (opt-in) decode a fixed number of rows; more target-carrying rows than that would be dropped from
                 # the loss -- never silently (checked here, where the step's scalars are read back anyway)
                 raise RuntimeError("loss_aware_heads: more rows carry a target than the row capacity; raise capacity_frac or use the full heads")
+            if "padding_row_overflow" in reduced_metrics and float(reduced_metrics["padding_row_overflow"]) > 0:
+                raise RuntimeError("skip_padding: more valid rows than the static row capacity, the rows beyond it were dropped from the step; "
+                                   "raise the fraction or use skip_padding = \"exact\"")
             total = sum(reduced_metrics["loss"].values())
             writer.add_scalar("learning_rate/train", float(scheduler.get_last_lr()[0]), global_step=global_step)
             writer.add_scalar("loss/train", float(total), global_step=global_step)

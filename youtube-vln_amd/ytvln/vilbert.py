@@ -106,6 +106,55 @@ class BertConfig:
 class _Runtime:
     drop: Optional[DropoutState] = None
     ffn_recompute: bool = False          # BertEncoder.recompute == "ffn", for the duration of that encoder's forward (read by _ffn_block)
+    plans = None                         # BertModel.skip_padding: (text RowsPlan | None, image RowsPlan | None) while such a forward, or the
+                                         # recomputation of one of its layers, runs; None = every row of both streams is padded (the default)
+
+
+def _plan(side: int):
+    """The RowsPlan of the text (0) / image (1) stream when its hidden states are packed rows [1, capacity, H], else None."""
+    return None if _Runtime.plans is None else _Runtime.plans[side]
+
+
+def _with_plans(plans, fn, *args):
+    """fn(*args) with `plans` installed: a recomputed layer runs in the backward pass, long after its forward's plans were taken down."""
+    prev, _Runtime.plans = _Runtime.plans, plans
+    try:
+        return fn(*args)
+    finally:
+        _Runtime.plans = prev
+
+
+SKIP_PADDING_TILE = 256          # packed capacities are whole 256-row GEMM tiles
+
+
+def _skip_padding_spec(value):
+    """BertModel.skip_padding, validated -> None or a (text, image) pair whose entries are "exact" or a fraction in (0, 1]."""
+    def one(v):
+        if isinstance(v, str):
+            return v == "exact"
+        return isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 < float(v) <= 1.0
+    if value is None:
+        return None
+    if one(value):
+        return (value, value)
+    if isinstance(value, (tuple, list)) and len(value) == 2 and all(one(v) and not isinstance(v, str) for v in value):
+        return (value[0], value[1])
+    raise ValueError(f"BertModel.skip_padding = {value!r}: expected None, a fraction in (0, 1], a (text, image) pair of such fractions, or \"exact\"")
+
+
+def _side_plan(mask, spec):
+    """RowsPlan of one padding mask [N, L] (non-zero = valid).  A fraction: static capacity, no host sync, capturable.  "exact": the count is read
+    on the host (one sync) and rounded up to a whole tile."""
+    rows = mask.numel()
+    if spec == "exact":
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('BertModel.skip_padding = "exact" reads the number of valid rows on the host and cannot be captured into a graph; '
+                               "give a static capacity (a fraction in (0, 1])")
+        count = int((mask != 0).sum())
+        cap = min(rows, max(1, -(-count // SKIP_PADDING_TILE)) * SKIP_PADDING_TILE)
+    else:
+        cap = ops.rows_capacity(rows, spec)
+    return ops.rows_plan(mask, cap)
 
 
 def _begin_forward(module: nn.Module, device) -> None:
@@ -323,6 +372,7 @@ class _SelfAttentionBase(nn.Module):
     """Shared forward of BertSelfAttention / BertImageSelfAttention."""
 
     want_probs = False
+    _side = 0          # the stream whose RowsPlan (BertModel.skip_padding) this site reads: 0 text, 1 image
 
     def _build(self, hidden, heads, p_attn):
         if hidden % heads != 0:
@@ -342,10 +392,18 @@ class _SelfAttentionBase(nn.Module):
     def forward_res(self, hidden_states, attention_mask):
         """(context, probs, hidden_states-for-the-residual): the third value is what the caller's `LayerNorm(dense(context) + input)`
         must use as `input` so that the two gradients of `hidden_states` meet inside the projection's input-gradient GEMM."""
-        n, t, _ = hidden_states.shape
+        plan = _plan(self._side)
+        if plan is None:
+            n, t, _ = hidden_states.shape
+        else:          # packed rows [1, capacity, H]: the mask carries the padded geometry
+            t = attention_mask.shape[-1]
+            n = plan.rows // t
         mask, bias = _self_mask(attention_mask, n, t, self.num_attention_heads)
         qkv, residual = _PackedQKV.project_res(hidden_states, self.query, self.key, self.value)
-        qkv = qkv.view(n * t, 3 * self.all_head_size)
+        if plan is None:
+            qkv = qkv.view(n * t, 3 * self.all_head_size)
+        else:          # the attention kernels read the padded [N*T, 3H] layout: masks, biases, dropout and probabilities keep padded coordinates
+            qkv = ops.rows_unpack(qkv.view(plan.capacity, 3 * self.all_head_size), plan)
         p = _p(self, self.dropout.p)
         st = _drop_state(self, qkv) if p > 0 else None
         extra = () if bias is None else (bias,)          # (no bias: the call, and the launch behind it, as it always was)
@@ -359,6 +417,8 @@ class _SelfAttentionBase(nn.Module):
                 h = self.all_head_size
                 probs = ops.attn_probs(qkv, 0, 3 * h, qkv, h, 3 * h, mask, lse, n, self.num_attention_heads, t, t,
                                        self.attention_head_size, 1.0 / math.sqrt(self.attention_head_size), bias=bias)
+        if plan is not None:
+            return ops.rows_pack(out, plan).view(1, plan.capacity, self.all_head_size), probs, residual
         return out.view(n, t, self.all_head_size), probs, residual
 
 
@@ -452,6 +512,8 @@ class BertLayer(nn.Module):
 
 
 class BertImageSelfAttention(_SelfAttentionBase):
+    _side = 1
+
     def __init__(self, config):
         super().__init__()
         self._build(config.v_hidden_size, config.v_num_attention_heads, config.v_attention_probs_dropout_prob)
@@ -530,8 +592,13 @@ class BertBiAttention(nn.Module):
         """forward() plus the two stream inputs as they leave the projections' autograd nodes (the residual values BertBiOutput adds):
         returned, not parked on the module -- no graph stays pinned between calls and a direct forward() cannot leave a stale pair behind
         (ADVICE r2).  BertConnectionLayer calls this form."""
-        n, r, _ = input_tensor1.shape
-        t = input_tensor2.shape[1]
+        plan_t, plan_v = _plan(0), _plan(1)
+        if plan_v is None:
+            n, r, _ = input_tensor1.shape
+        else:          # packed rows: the masks carry the padded geometry
+            r = attention_mask1.shape[-1]
+            n = plan_v.rows // r
+        t = input_tensor2.shape[1] if plan_t is None else attention_mask2.shape[-1]
         hb = self.all_head_size
         # use_co_attention_mask (vilbert.py:581-582, 603-604): co_attention_mask [N,1,R,T] is added to the scores of regions over tokens as it is
         # and to those of tokens over regions through its transposed VIEW (the kernels read it through swapped strides: no copy)
@@ -547,9 +614,13 @@ class BertBiAttention(nn.Module):
         # projections' autograd nodes (ops.LinearFn passthrough) so the three gradients meet inside the input-gradient GEMMs
         q1, res1 = ops.linear_res(input_tensor1, self.query1.weight, self.query1.bias)
         kv1, res1 = ops.linear_res(res1, ops.pack_rows(self.key1.weight, self.value1.weight), ops.pack_rows(self.key1.bias, self.value1.bias))
+        if plan_v is not None:
+            q1, kv1 = ops.rows_unpack(q1.view(-1, hb), plan_v), ops.rows_unpack(kv1.view(-1, 2 * hb), plan_v)
         with ops.TwoStream.side(input_tensor2):         # the text side's projections: second HIP stream when two-stream mode is on
             q2, res2 = ops.linear_res(input_tensor2, self.query2.weight, self.query2.bias)
             kv2, res2 = ops.linear_res(res2, ops.pack_rows(self.key2.weight, self.value2.weight), ops.pack_rows(self.key2.bias, self.value2.bias))
+            if plan_t is not None:
+                q2, kv2 = ops.rows_unpack(q2.view(-1, hb), plan_t), ops.rows_unpack(kv2.view(-1, 2 * hb), plan_t)
         ops.TwoStream.join(q2, kv2)
         q1, kv1, q2, kv2 = q1.view(n * r, hb), kv1.view(n * r, 2 * hb), q2.view(n * t, hb), kv2.view(n * t, 2 * hb)
         p1, p2 = _p(self, self.dropout1.p), _p(self, self.dropout2.p)
@@ -558,6 +629,8 @@ class BertBiAttention(nn.Module):
         extra = () if bias2 is None else (bias1, bias2)
         ctx1, ctx2, lse1, lse2 = ops.CoAttentionFn.apply(q1, kv1, q2, kv2, m1, m2, n, r, t, self.num_attention_heads, p1, p2,
                                                          st.tensor if st else None, s1, s2, *extra)
+        out1 = ctx1.view(n, t, hb) if plan_t is None else ops.rows_pack(ctx1, plan_t).view(1, plan_t.capacity, hb)
+        out2 = ctx2.view(n, r, hb) if plan_v is None else ops.rows_pack(ctx2, plan_v).view(1, plan_v.capacity, hb)
         ops.TwoStream.mark()                            # both context tensors exist: the text side may go on from here
         probs = (None, None)
         if self.want_probs:
@@ -568,7 +641,7 @@ class BertBiAttention(nn.Module):
                 pr2 = ops.attn_probs(q1, 0, hb, kv2, 0, 2 * hb, m2, lse2, n, self.num_attention_heads, r, t,
                                      self.attention_head_size, sc, bias=bias2)
                 probs = (pr1, pr2)
-        return ctx1.view(n, t, hb), ctx2.view(n, r, hb), probs, res1, res2
+        return out1, out2, probs, res1, res2
 
 
 class BertBiOutput(nn.Module):
@@ -718,7 +791,7 @@ class BertEncoder(nn.Module):
                         x, pr = layers[idx](x, mask)
                 elif recompute_layers:
                     # (a trainable per-score mask is differentiated like the hidden states; a constant one is carried along)
-                    x, pr = _recompute_layer(lambda h, m, layer=layers[idx]: layer(h, m)[0],
+                    x, pr = _recompute_layer(lambda h, m, layer=layers[idx], plans=_Runtime.plans: _with_plans(plans, layer, h, m)[0],
                                              *(((x, mask), ()) if mask.requires_grad else ((x,), (mask,)))), None
                 else:
                     x, pr = layers[idx](x, mask)
@@ -753,7 +826,8 @@ class BertEncoder(nn.Module):
                 c_layer, use_co = self.c_layer[count], bool(self.use_co_attention_mask)
                 co_grad = torch.is_tensor(co_attention_mask) and co_attention_mask.requires_grad          # a trainable co_attention_mask
                 image_embedding, txt_embedding = _recompute_layer(
-                    lambda hv, ht, co, mv, mt, layer=c_layer, use_co=use_co: layer(hv, mv, ht, mt, co, use_co)[:2],
+                    lambda hv, ht, co, mv, mt, layer=c_layer, use_co=use_co, plans=_Runtime.plans:
+                        _with_plans(plans, layer, hv, mv, ht, mt, co, use_co)[:2],
                     (image_embedding, txt_embedding) + ((co_attention_mask,) if co_grad else ()),
                     (() if co_grad else (co_attention_mask,)) + (image_attention_mask, txt_attention_mask))
             elif self.with_coattention:
@@ -988,6 +1062,22 @@ class BertModel(BertPreTrainedModel):
         args = getattr(config, "args", None)
         if args is not None and hasattr(args, "recompute"):
             self.encoder.recompute = args.recompute
+        if args is not None and hasattr(args, "skip_padding"):
+            self.skip_padding = args.skip_padding
+        self.padding_overflow = None          # device int64 [2] (text, image) once a skip_padding forward has run: valid rows that did not fit, summed
+
+    # Extension, opt-in (a plain attribute like encoder.recompute; taken from config.args.skip_padding when that field exists): padding-free
+    # execution.  Both streams run their row-wise kernels -- Linear / FFN GEMMs, LayerNorm, activations, the image embedding -- on the VALID rows
+    # of the batch only, packed into [1, capacity, H]; the attention sites move rows to the padded layout and back (ops.rows_unpack / rows_pack),
+    # and the last hidden states come back as [N, T, H] / [N, R, H] with exact zeros on padded rows.
+    #   None              (default) today's path, bit for bit: no plan, no new launch.
+    #   f in (0, 1]       static capacity min(rows, ceil(f * rows / 256) * 256) per side, or a (text, image) pair of fractions.  No host sync,
+    #                     capturable.  Valid rows beyond the capacity are DROPPED and counted in `padding_overflow` (train_step reports it).
+    #   "exact"           the count of valid rows is read on the host (one sync per side) and rounded up to 256.  Raises under stream capture.
+    # A side whose mask argument is None stays padded.  Valid are the rows whose mask entry is non-zero; padded rows are keys behind a -10000
+    # additive mask (their softmax weight is exactly 0) and no loss reads them, so losses and gradients are those of the padded run at p = 0.
+    # With dropout on, the LayerNorm / FFN / image-embedding sites hash packed coordinates: other masks of the same distribution.
+    skip_padding = None
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
                 co_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
@@ -1016,24 +1106,57 @@ class BertModel(BertPreTrainedModel):
                 ext_co = (co_attention_mask.unsqueeze(1) * 5.0).to(torch.float32)
 
         ts = ops.TwoStream
+        plan_t, plan_v = self._plans(attention_mask, image_attention_mask)          # (None, None) unless skip_padding is set
         try:
             if not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE):
                 ts.begin(input_imgs.device)              # two-stream mode: the text side starts at its embeddings
                 _share_drop_state()
+                if ts.active and plan_t is not None:          # made on the main stream in front of the fork, read by the text side's launches
+                    plan_t.record_stream(ts.side_stream(input_imgs.device))
             with ts.side(input_txt, token_type_ids, ext_t):
-                embedding_output = self.embeddings(input_txt, token_type_ids)
+                embedding_output = self.embeddings(input_txt, token_type_ids)          # padded ids: the kernel derives the position from row % T
+                if plan_t is not None:
+                    embedding_output = ops.rows_pack(embedding_output, plan_t).view(1, plan_t.capacity, -1)
+            if plan_v is not None:          # the 2048-wide feature projection and the fused embedding run on packed rows (bf16 mode: packed, then cast)
+                input_imgs = ops.rows_pack(input_imgs if input_imgs.dtype == torch.float32 else input_imgs.float(), plan_v).unsqueeze(0)
+                image_loc = ops.rows_pack(image_loc if image_loc.dtype == torch.float32 else image_loc.float(), plan_v).unsqueeze(0)
             v_embedding_output = self.v_embeddings(input_imgs, image_loc)
+            _Runtime.plans = (plan_t, plan_v) if (plan_t is not None or plan_v is not None) else None
             encoded_layers_t, encoded_layers_v, all_attention_mask = self.encoder(
                 embedding_output, v_embedding_output, ext_t, ext_v, ext_co,
                 output_all_encoded_layers=output_all_encoded_layers, output_all_attention_masks=output_all_attention_masks)
         finally:
             ts.active = False
+            _Runtime.plans = None
+        if plan_t is not None:          # back to [N, T, H]: padded rows are exact zeros
+            encoded_layers_t = [ops.rows_unpack(h.view(plan_t.capacity, -1), plan_t).view(n, t, -1) for h in encoded_layers_t]
+        if plan_v is not None:
+            encoded_layers_v = [ops.rows_unpack(h.view(plan_v.capacity, -1), plan_v).view(nv, r, -1) for h in encoded_layers_v]
         sequence_output_t, sequence_output_v = encoded_layers_t[-1], encoded_layers_v[-1]
         pooled_output_t = self.t_pooler(sequence_output_t)
         pooled_output_v = self.v_pooler(sequence_output_v)
         if not output_all_encoded_layers:
             encoded_layers_t, encoded_layers_v = encoded_layers_t[-1], encoded_layers_v[-1]
         return encoded_layers_t, encoded_layers_v, pooled_output_t, pooled_output_v, all_attention_mask
+
+
+    def _plans(self, attention_mask, image_attention_mask):
+        """(text RowsPlan | None, image RowsPlan | None) of this forward; accumulates the rows that did not fit into `padding_overflow`."""
+        spec = _skip_padding_spec(self.skip_padding)
+        if spec is None:
+            return None, None
+        if self.encoder.in_batch_pairs or self.encoder.FAST_MODE:
+            raise NotImplementedError("BertModel.skip_padding with in_batch_pairs / fast_mode: these modes rebuild one stream's rows from the other "
+                                      "batch in padded coordinates; run them with skip_padding = None")
+        plans = [None if m is None else _side_plan(m, s) for m, s in ((attention_mask, spec[0]), (image_attention_mask, spec[1]))]
+        live = [p for p in plans if p is not None]
+        if live:
+            dev = live[0].counts.device
+            if self.padding_overflow is None or self.padding_overflow.device != dev:
+                self.padding_overflow = torch.zeros(2, dtype=torch.int64, device=dev)
+            zero = self.padding_overflow.new_zeros(())
+            self.padding_overflow += torch.stack([zero if p is None else p.counts[1] for p in plans])
+        return plans[0], plans[1]
 
 
 class BertForMultiModalPreTraining(BertPreTrainedModel):
