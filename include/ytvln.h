@@ -210,14 +210,16 @@ int ytvln_rows_move_bf16(const uint16_t* x, int64_t ldx, int64_t x_rows, const i
  * inside the sqrt) together with the dropout/add that always precedes it (:322-324, :365-367, :641-648) or follows it
  * (:254-255, :1367-1368).
  *   s = (p_pre > 0 ? dropout(x) : x) + (res ? res : 0);  y = gamma * (s - mean) * rstd + beta;  p_post: y = dropout(y)
- * s_out receives s (may alias x; may be NULL when not training), mean/rstd are [rows] (may be NULL). */
+ * s_out receives s (may alias x; may be NULL when not training), mean/rstd are [rows] (may be NULL).
+ * At most ONE of p_pre / p_post may be > 0, in the forward and in the backward, fp32 and bf16: both masks of a call would come from the same
+ * (key, site, row, vector) draw -- fully correlated, identical at p_pre == p_post -- so the combination returns an error. */
 int ytvln_ln_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y, float* s_out,
                      float* mean, float* rstd, int64_t rows, int H, float eps, float p_pre, float p_post,
                      const int64_t* rng, int64_t site, void* stream);
 
 /* Backward of the above.  ds = dL/ds (gradient w.r.t. the residual input), dx = gradient w.r.t. x (written only when
  * p_pre > 0; otherwise dx == ds and dx may be NULL).  partial is [nblocks, 2, H] (dgamma then dbeta partial sums, to be
- * reduced with ytvln_colsum_f32); nblocks = ytvln_ln_bwd_blocks(rows). */
+ * reduced with ytvln_colsum_f32); nblocks = ytvln_ln_bwd_blocks(rows).  p_pre and p_post both > 0: an error, as in the forward. */
 int ytvln_ln_bwd_blocks(int64_t rows);
 int ytvln_ln_bwd_f32(const float* dy, const float* s, const float* mean, const float* rstd, const float* gamma,
                      float* ds, float* dx, float* partial, int64_t rows, int H, float p_pre, float p_post,
@@ -261,7 +263,8 @@ int ytvln_dropout_f32(const float* x, float* y, int64_t n, float p, const int64_
 /* bf16-resident forms of the five kernels above (BASELINE configs[4]): rows of x / res / y / s_out / dy / s / ds / dx are bf16 (8-byte aligned),
  * the arithmetic is the fp32 one (values widened on load, rounded to nearest even on store), statistics, gamma / beta, their gradient partials and
  * the embedding tables stay fp32; the dropout masks are the SAME as in the fp32 kernels (one Philox draw per group of four elements).
- * ytvln_ln_bwd_bf16: ds / dx may be NULL when the caller only wants ds_f32, an fp32 copy of ds for the embedding-table gradient kernels. */
+ * ytvln_ln_bwd_bf16: ds / dx may be NULL when the caller only wants ds_f32, an fp32 copy of ds for the embedding-table gradient kernels.
+ * ytvln_ln_fwd_bf16 / ytvln_ln_bwd_bf16 refuse p_pre and p_post both > 0 like their fp32 forms. */
 int ytvln_ln_fwd_bf16(const uint16_t* x, const uint16_t* res, const float* gamma, const float* beta, uint16_t* y, uint16_t* s_out, float* mean,
                       float* rstd, int64_t rows, int H, float eps, float p_pre, float p_post, const int64_t* rng, int64_t site, void* stream);
 int ytvln_ln_bwd_bf16(const uint16_t* dy, const uint16_t* s, const float* mean, const float* rstd, const float* gamma, uint16_t* ds, uint16_t* dx,

@@ -129,7 +129,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnArgs a) {
             }
             s[j] = v;
         }
-        const float mu = wave_sum(sum) * invH;
+        // a true division: sum * (1 / H) with the rounded reciprocal leaves the mean of a CONSTANT row one ulp off for some H (252, 1020: 2.5 ->
+        // 2.5000002), and with eps = 1e-12 that ulp is the whole "variance" -- xhat came out -0.23 instead of 0.  The row sum of a constant row is
+        // exact, so the correctly rounded quotient is the constant itself, as in the reference's x.mean(-1).
+        const float mu = wave_sum(sum) / (float)a.H;
         float sq = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -354,7 +357,7 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16x8_kernel(const LnArgs a) {
                 for (int e = 0; e < 8; e += 2) sum += s[j].v[e] + s[j].v[e + 1];
             }
         }
-        const float mu = wave_sum(sum) * invH;
+        const float mu = wave_sum(sum) / (float)a.H;          // a true division: see ln_fwd_kernel
         float sq = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j)
@@ -808,6 +811,7 @@ extern "C" int ytvln_ln_fwd_f32(const float* x, const float* res, const float* g
                "ln_fwd: pointers must be 16-byte aligned");
     YT_REQUIRE(p_pre >= 0.f && p_pre < 1.f && p_post >= 0.f && p_post < 1.f, "ln_fwd: dropout p out of range");
     YT_REQUIRE(!(p_pre > 0.f || p_post > 0.f) || rng, "ln_fwd: dropout needs rng state");
+    YT_REQUIRE(!(p_pre > 0.f && p_post > 0.f), "ln_fwd: p_pre and p_post both > 0 (the two masks would come from one draw)");
     if (rows == 0) return 0;
     LnArgs a = {};
     a.x = x; a.res = res; a.gamma = gamma; a.beta = beta; a.y = y; a.s_out = s_out; a.mean = mean; a.rstd = rstd;
@@ -867,6 +871,7 @@ extern "C" int ytvln_ln_bwd_f32(const float* dy, const float* s, const float* me
     YT_REQUIRE(ln_shape_ok(H), "ln_bwd: H=%d unsupported", H);
     YT_REQUIRE(al16(dy) && al16(s) && al16(ds) && al16(gamma) && (!dx || al16(dx)), "ln_bwd: pointers must be 16-byte aligned");
     YT_REQUIRE(!(p_pre > 0.f || p_post > 0.f) || rng, "ln_bwd: dropout needs rng state");
+    YT_REQUIRE(!(p_pre > 0.f && p_post > 0.f), "ln_bwd: p_pre and p_post both > 0 (the two masks would come from one draw)");
     YT_REQUIRE(!(p_pre > 0.f) || dx, "ln_bwd: p_pre > 0 needs dx");
     if (rows == 0) return 0;
     LnBwdArgs a;
@@ -1008,6 +1013,7 @@ extern "C" int ytvln_ln_fwd_bf16(const uint16_t* x, const uint16_t* res, const f
     YT_REQUIRE(al8(x) && al8(y) && al16(gamma) && al16(beta) && (!res || al8(res)) && (!s_out || al8(s_out)), "ln_fwd_bf16: misaligned pointer");
     YT_REQUIRE(p_pre >= 0.f && p_pre < 1.f && p_post >= 0.f && p_post < 1.f, "ln_fwd_bf16: dropout p out of range");
     YT_REQUIRE(!(p_pre > 0.f || p_post > 0.f) || rng, "ln_fwd_bf16: dropout needs rng state");
+    YT_REQUIRE(!(p_pre > 0.f && p_post > 0.f), "ln_fwd_bf16: p_pre and p_post both > 0 (the two masks would come from one draw)");
     if (rows == 0) return 0;
     LnArgs a = {};
     a.x = x; a.res = res; a.gamma = gamma; a.beta = beta; a.y = y; a.s_out = s_out; a.mean = mean; a.rstd = rstd;
@@ -1068,6 +1074,7 @@ extern "C" int ytvln_ln_bwd_bf16(const uint16_t* dy, const uint16_t* s, const fl
     YT_REQUIRE(ln_shape_ok(H), "ln_bwd_bf16: H=%d unsupported", H);
     YT_REQUIRE(al8(dy) && al8(s) && (!ds || al8(ds)) && al16(gamma) && (!dx || al8(dx)) && (!ds_f32 || al16(ds_f32)), "ln_bwd_bf16: misaligned pointer");
     YT_REQUIRE(!(p_pre > 0.f || p_post > 0.f) || rng, "ln_bwd_bf16: dropout needs rng state");
+    YT_REQUIRE(!(p_pre > 0.f && p_post > 0.f), "ln_bwd_bf16: p_pre and p_post both > 0 (the two masks would come from one draw)");
     YT_REQUIRE(!(p_pre > 0.f) || dx, "ln_bwd_bf16: p_pre > 0 needs dx");
     if (rows == 0) return 0;
     LnBwdArgs a;

@@ -976,14 +976,24 @@ def _ln_bwd(dy, s, mean, rstd, gamma, rows, H, p_pre, p_post, rng, site, gb_targ
     return ds, dx, gb[:H], gb[H:]
 
 
+def _one_sided_dropout(p_pre, p_post) -> None:
+    """The row kernels draw the dropout in front of the LayerNorm and the one behind it from the same (key, site, row, vector) bits: asked for both,
+    the two masks would be fully correlated (identical at p_pre == p_post).  No site of the model uses both, so the combination is refused here and
+    again at the C ABI."""
+    if p_pre > 0 and p_post > 0:
+        raise RuntimeError(f"add_layer_norm: p_pre = {p_pre} and p_post = {p_post} are both > 0; one call draws one mask -- use p_pre or p_post "
+                           "and a separate ops.dropout for the other")
+
+
 class AddLayerNormFn(torch.autograd.Function):
     """y = LN(dropout(x) + residual) [dropout after] -- BertLayerNorm with its surrounding dropout / residual add, on rows of `fmt` (statistics,
-    gamma / beta and their gradients fp32); saves s = dropout(x) + residual in that format."""
+    gamma / beta and their gradients fp32); saves s = dropout(x) + residual in that format.  At most one of p_pre / p_post may be > 0."""
 
     @staticmethod
     def forward(ctx, x, res, gamma, beta, eps, p_pre, p_post, rng, site, fmt=_F32):
         ctx.set_materialize_grads(False)
         ctx.fmt = fmt
+        _one_sided_dropout(p_pre, p_post)
         _check(x, "x", fmt.dtype)
         H = x.shape[-1]
         xc = x if x.is_contiguous() else x.contiguous()
@@ -1020,6 +1030,7 @@ class AddLayerNormFn(torch.autograd.Function):
 def add_layer_norm(x, res, gamma, beta, eps=1e-12, p_pre=0.0, p_post=0.0, drop: Optional[DropoutState] = None) -> Tensor:
     if (p_pre > 0 or p_post > 0) and drop is None:
         raise RuntimeError("dropout requested without a DropoutState")
+    _one_sided_dropout(p_pre, p_post)
     use = drop is not None and (p_pre > 0 or p_post > 0)
     return AddLayerNormFn.apply(x, res, gamma, beta, eps, p_pre if use else 0.0, p_post if use else 0.0,
                                 drop.tensor if use else None, drop.next_site() if use else 0, _format_of(x))
