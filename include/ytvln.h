@@ -522,6 +522,24 @@ int ytvln_ema_update(const float* p, float* e, const void* chunks, int nchunks, 
  * is not NULL, writes p_bf16[i] = bf16(new p[i]) (round to nearest even) at the same offsets.  All arenas 16-byte aligned.  16 bytes per
  * parameter, 18 with the copy. */
 int ytvln_ema_swap(float* p, float* e, uint16_t* p_bf16, const void* chunks, int nchunks, void* stream);
+/* Per-tensor gradient / weight statistics (the reference has none): two read-only launches per chunk table behind the update launches, so
+ * g is the gradient the update read and p the parameter it wrote (unchanged on a skipped step: there is no clip record here, a skipped step
+ * reports as any other).  No atomics, every order fixed by the tables alone: two launches on the same inputs give the same bits.  An
+ * element is non-finite when it is an infinity or a NaN; sums and maxima run over the finite elements only.
+ *   stage 1: one workgroup per record; reads [offset, offset + length) of p and g and nothing else (8 bytes per parameter, 6 with bf16
+ * gradients) and writes partials[4i .. 4i+3] = {sum g^2, max |g|, sum p^2, max |p|} (sums accumulated in fp32) and bad[2i], bad[2i+1] = the
+ * number of non-finite elements of g and of p in record i.  g_dtype: YTVLN_DT_F32 or YTVLN_DT_BF16, nothing else (bf16 widens exactly).
+ * Arenas and partials 16-byte, bad 8-byte aligned. */
+int ytvln_tensor_stats_stage1(const float* p, const void* g, int g_dtype, const void* chunks, int nchunks, float* partials, int32_t* bad,
+                              void* stream);
+/*   stage 2: one wave per tensor of the table (tensor_first, rec_tensor as for ytvln_lamb_trust; any number of records per tensor).  Sums
+ * the tensor's partials in fp64 in record order, takes the maxima and writes, with k = rec_tensor[tensor_first[t]],
+ *   stats[4k .. 4k+3] = {float(grad_scale * sqrt(sum g^2)) (in double, rounded once), float(grad_scale) * max |g| (one fp32 product),
+ *                        float(sqrt(sum p^2)), max |p|}      an empty finite set gives 0 and 0; 16-byte aligned
+ *   counts[3k .. 3k+2] = {non-finite elements of g, of p, launches so far in which this tensor had a non-finite g}   int64; the third entry
+ * is read, incremented and written here, as ytvln_grad_clip_coef does for clip[3]. */
+int ytvln_tensor_stats_stage2(const float* partials, const int32_t* bad, const int32_t* tensor_first, const int32_t* rec_tensor,
+                              int ntensors, float grad_scale, float* stats, int64_t* counts, void* stream);
 
 /* ---- heads of the downstream-task model (VILBertForVLTasks / SimpleClassifier, vilbert.py:1457-1535) -------------------------------------
  * None of these uses an atomic: every reduction runs in an order fixed by the shapes alone, so two launches on the same inputs give the

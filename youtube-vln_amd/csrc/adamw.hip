@@ -13,6 +13,8 @@
 // Opt-in EMA of the weights keeps a shadow arena with the offsets of the parameter arena: ema_update_kernel is a launch of its own behind the
 // update (12 bytes per parameter; fused into the update it would be 8, at the price of a sixth instantiation of the audited kernels), and
 // ema_swap_kernel exchanges parameters and shadow for evaluation (16 bytes per parameter, 18 with the bf16 copy).
+// Opt-in per-tensor statistics read p and g once more behind the update (tensor_stats_stage1_kernel: 8 bytes per parameter, 6 with bf16
+// gradients) and reduce per tensor (tensor_stats_stage2_kernel): norms, maxima and counts of non-finite elements, one row per arena tensor.
 #include "common.h"
 
 namespace ytvln {
@@ -355,6 +357,114 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ P, fl
     }
 }
 
+// ---- per-tensor gradient / weight statistics, opt-in: which tensor of the arena went non-finite, and how large everything else is ------------
+// Two read-only launches per chunk table behind the update (and the EMA): g is the gradient the update read, p the parameter it wrote.
+// An element is finite when its exponent field is not all ones; |x| of a finite x is compared as an integer (for non-negative floats the
+// integer order of the bits is the order of the values), so a maximum is one of the inputs bit for bit and NaNs need no special case.
+// A non-finite element enters the sum as the square of 0 (fma(0, 0, s) == s exactly), the maximum as 0, and is counted.
+__device__ __forceinline__ void stat1(float x, float& ss, uint32_t& mx, int& bad) {
+    const uint32_t a = __float_as_uint(x) & 0x7fffffffu;
+    const bool fin = a < 0x7f800000u;
+    const float xf = fin ? x : 0.f;
+    ss = __builtin_fmaf(xf, xf, ss);
+    mx = max(mx, fin ? a : 0u);
+    bad += fin ? 0 : 1;
+}
+__device__ __forceinline__ void stat4(const float4& x, float& ss, uint32_t& mx, int& bad) {
+    stat1(x.x, ss, mx, bad); stat1(x.y, ss, mx, bad); stat1(x.z, ss, mx, bad); stat1(x.w, ss, mx, bad);
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Stage 1: one workgroup per chunk record; reads [off, off + len) of p and g and nothing else (8 bytes per parameter, 6 with bf16 gradients).
+// Writes per record the four fp32 partials {sum g^2, max |g|, sum p^2, max |p|} over the finite elements and the two int32 counts of
+// non-finite elements of g and of p.  The sums are accumulated as in grad_sumsq_kernel: a thread takes the vectors t, t + 256, ... of the
+// record (loads issued four of each arena at a time) and adds the squares into ONE fp32 accumulator per sum in element order (a record of
+// 16384 elements: 64 serial fmas per thread), then the workgroup sums in a fixed tree: six butterfly levels inside each wave, two across
+// the four waves.  Maxima and counts are exact in any order.  No atomics: a partial is the same bits on every run.
+template <typename GT>
+__global__ __launch_bounds__(256) void tensor_stats_stage1_kernel(const float* __restrict__ P, const GT* __restrict__ G,
+                                                                  const AdamChunk* __restrict__ chunks, float4* __restrict__ partials,
+                                                                  int2* __restrict__ bad) {
+    __shared__ float2 wsum[4];
+    __shared__ uint2 wmax[4];
+    __shared__ int2 wbad[4];
+    const AdamChunk c = chunks[blockIdx.x];
+    const float* p = P + c.off; const GT* g = G + c.off;
+    const int64_t n4 = ((c.off & 3) == 0) ? (c.len >> 2) : 0;
+    float sg = 0.f, sp = 0.f;
+    uint32_t mg = 0u, mp = 0u;
+    int bg = 0, bp = 0;
+    for (int64_t i = threadIdx.x; i < n4; i += 4 * 256) {
+        float4 x[4], y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool in = i + k * 256 < n4;
+            x[k] = in ? load_g4(g, i + k * 256) : make_float4(0.f, 0.f, 0.f, 0.f);
+            y[k] = in ? reinterpret_cast<const float4*>(p)[i + k * 256] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { stat4(x[k], sg, mg, bg); stat4(y[k], sp, mp, bp); }
+    }
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < c.len; i += 256) { stat1(load_g1(g, i), sg, mg, bg); stat1(p[i], sp, mp, bp); }
+    sg = wave_sum(sg); sp = wave_sum(sp);
+    mg = wave_max_u32(mg); mp = wave_max_u32(mp);
+    bg = wave_sum_i32(bg); bp = wave_sum_i32(bp);
+    if ((threadIdx.x & 63) == 0) {
+        wsum[threadIdx.x >> 6] = make_float2(sg, sp); wmax[threadIdx.x >> 6] = make_uint2(mg, mp); wbad[threadIdx.x >> 6] = make_int2(bg, bp);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = make_float4((wsum[0].x + wsum[1].x) + (wsum[2].x + wsum[3].x),
+                                           __uint_as_float(max(max(wmax[0].x, wmax[1].x), max(wmax[2].x, wmax[3].x))),
+                                           (wsum[0].y + wsum[1].y) + (wsum[2].y + wsum[3].y),
+                                           __uint_as_float(max(max(wmax[0].y, wmax[1].y), max(wmax[2].y, wmax[3].y))));
+        bad[blockIdx.x] = make_int2((wbad[0].x + wbad[1].x) + (wbad[2].x + wbad[3].x), (wbad[0].y + wbad[1].y) + (wbad[2].y + wbad[3].y));
+    }
+}
+
+// Stage 2: one wave per tensor of the table, `first` / `rec_tensor` as in lamb_trust_kernel.  Lane l adds the partials of records
+// first[t] + l, + 64, ... in order in fp64 and takes their maxima, then a fixed butterfly over the 64 lanes.  Lane 0 writes the tensor's row
+// k = rec_tensor[first[t]]: stats[k] = {gscale * sqrt(sum g^2) evaluated in double and rounded once, float(gscale) * max |g| (one fp32
+// product), sqrt(sum p^2), max |p|} and counts[k] = {non-finite g, non-finite p, steps so far with a non-finite g}: the third entry is read,
+// incremented and written here, as grad_clip_coef_kernel does for clip[3].
+__global__ __launch_bounds__(64) void tensor_stats_stage2_kernel(const float4* __restrict__ partials, const int2* __restrict__ bad,
+                                                                 const int32_t* __restrict__ first, const int32_t* __restrict__ rec_tensor,
+                                                                 float gscale, float4* __restrict__ stats, int64_t* __restrict__ counts) {
+    const int lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
+    if (hi <= lo) return;
+    double sg = 0.0, sp = 0.0;
+    uint32_t mg = 0u, mp = 0u;
+    long long bg = 0, bp = 0;
+    for (int i = lo + (int)threadIdx.x; i < hi; i += 64) {
+        const float4 x = partials[i];
+        const int2 b = bad[i];
+        sg += (double)x.x; sp += (double)x.z;
+        mg = max(mg, __float_as_uint(x.y)); mp = max(mp, __float_as_uint(x.w));
+        bg += b.x; bp += b.y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sg += __shfl_xor(sg, o, 64); sp += __shfl_xor(sp, o, 64);
+        bg += __shfl_xor(bg, o, 64); bp += __shfl_xor(bp, o, 64);
+    }
+    mg = wave_max_u32(mg); mp = wave_max_u32(mp);
+    if (threadIdx.x == 0) {
+        const int k = rec_tensor[lo];
+        stats[k] = make_float4((float)((double)gscale * sqrt(sg)), gscale * __uint_as_float(mg), (float)sqrt(sp), __uint_as_float(mp));
+        int64_t* row = counts + 3 * (int64_t)k;
+        row[0] = bg; row[1] = bp; row[2] = row[2] + (bg > 0 ? 1 : 0);
+    }
+}
+
 }  // namespace ytvln
 
 using namespace ytvln;
@@ -509,5 +619,37 @@ extern "C" int ytvln_ema_swap(float* p, float* e, uint16_t* p_bf16, const void* 
     if (nchunks == 0) return 0;
     hipLaunchKernelGGL(ema_swap_kernel, dim3(nchunks), dim3(256), 0, as_stream(stream), p, e, p_bf16, reinterpret_cast<const AdamChunk*>(chunks));
     YT_LAUNCH_CHECK("ema_swap");
+    return 0;
+}
+
+extern "C" int ytvln_tensor_stats_stage1(const float* p, const void* g, int g_dtype, const void* chunks, int nchunks, float* partials,
+                                         int32_t* bad, void* stream) {
+    YT_REQUIRE(p && g && chunks && partials && bad, "tensor_stats_stage1: null pointer");
+    YT_REQUIRE(g_dtype == YTVLN_DT_F32 || g_dtype == YTVLN_DT_BF16, "tensor_stats_stage1: g_dtype %d (fp32 or bf16 gradients only)", g_dtype);
+    YT_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)partials) & 15) == 0 && ((uintptr_t)bad & 7) == 0,
+               "tensor_stats_stage1: the arenas and the partials must be 16-byte, the counts 8-byte aligned");
+    YT_REQUIRE(nchunks >= 0, "tensor_stats_stage1: nchunks = %d", nchunks);
+    if (nchunks == 0) return 0;
+    const AdamChunk* ch = reinterpret_cast<const AdamChunk*>(chunks);
+    if (g_dtype == YTVLN_DT_F32)
+        hipLaunchKernelGGL(tensor_stats_stage1_kernel<float>, dim3(nchunks), dim3(256), 0, as_stream(stream), p, reinterpret_cast<const float*>(g),
+                           ch, reinterpret_cast<float4*>(partials), reinterpret_cast<int2*>(bad));
+    else
+        hipLaunchKernelGGL(tensor_stats_stage1_kernel<uint16_t>, dim3(nchunks), dim3(256), 0, as_stream(stream), p,
+                           reinterpret_cast<const uint16_t*>(g), ch, reinterpret_cast<float4*>(partials), reinterpret_cast<int2*>(bad));
+    YT_LAUNCH_CHECK("tensor_stats_stage1");
+    return 0;
+}
+
+extern "C" int ytvln_tensor_stats_stage2(const float* partials, const int32_t* bad, const int32_t* tensor_first, const int32_t* rec_tensor,
+                                         int ntensors, float grad_scale, float* stats, int64_t* counts, void* stream) {
+    YT_REQUIRE(partials && bad && tensor_first && rec_tensor && stats && counts, "tensor_stats_stage2: null pointer");
+    YT_REQUIRE((((uintptr_t)partials | (uintptr_t)stats) & 15) == 0 && (((uintptr_t)bad | (uintptr_t)counts) & 7) == 0,
+               "tensor_stats_stage2: the partials and the report rows must be 16-byte, both count buffers 8-byte aligned");
+    YT_REQUIRE(ntensors >= 0, "tensor_stats_stage2: ntensors = %d", ntensors);
+    if (ntensors == 0) return 0;
+    hipLaunchKernelGGL(tensor_stats_stage2_kernel, dim3(ntensors), dim3(64), 0, as_stream(stream), reinterpret_cast<const float4*>(partials),
+                       reinterpret_cast<const int2*>(bad), tensor_first, rec_tensor, grad_scale, reinterpret_cast<float4*>(stats), counts);
+    YT_LAUNCH_CHECK("tensor_stats_stage2");
     return 0;
 }

@@ -104,6 +104,8 @@ SIGNATURES = {
     "ytvln_lamb_stage2": [P, P, P, P, P, I32, P, P, P, P, P],
     "ytvln_ema_update": [P, P, P, I32, P, P, P],
     "ytvln_ema_swap": [P, P, P, P, I32, P],
+    "ytvln_tensor_stats_stage1": [P, P, I32, P, I32, P, P, P],
+    "ytvln_tensor_stats_stage2": [P, P, P, P, I32, F32, P, P, P],
     # heads of VILBertForVLTasks (csrc/heads.hip)
     "ytvln_weight_norm_workspace_elems": [I64],
     "ytvln_weight_norm_fwd_f32": [P, P, I64, P, P, P, P, P],

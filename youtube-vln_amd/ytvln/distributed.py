@@ -554,7 +554,9 @@ class GraphedTrainStep:
     defers EVERY update until the last group's partials exist (a global norm needs all of them): the exchange still overlaps, the update no
     longer does.  With clipping off phased is unchanged.  The LAMB trust ratio (AdamW.trust_ratio) is fixed at capture in the same way;
     split and single record its three launches per class where the update sits, and phased defers every update to the end of the step as
-    with clipping (the launches run over whole launch classes, which the gradient groups cut across).
+    with clipping (the launches run over whole launch classes, which the gradient groups cut across).  Per-tensor statistics
+    (AdamW.tensor_stats, fixed at capture too) follow the update where it sits in split and single; phased launches them once at the end of
+    the step on the stream the group updates ran on, before the compute stream waits for it: the per-group updates keep their overlap.
 
     With the bf16 exchange of the wrapped DataParallel (`grad_dtype`) every form packs what it exchanges into the optimizer's bf16 buffer
     right before the collective (split: at the end of graph A; single: inside the graph; phased: per group on the communication stream),
@@ -605,6 +607,8 @@ class GraphedTrainStep:
             optimizer.lamb_buffers()        # LAMB trust ratio on: its partials, ratios and report rows
         if hasattr(optimizer, "ema_setting") and optimizer.ema_setting() is not None:
             optimizer.ema_buffers()         # EMA of the weights on: its shadow arena
+        if hasattr(optimizer, "stats_setting") and optimizer.stats_setting():
+            optimizer.stats_buffers()       # per-tensor statistics on: their partials and report rows
         torch.cuda.synchronize()
         flat = optimizer.flat_grad()
         # the buffer the collectives work on: the fp32 arena, or its bf16 copy (same offsets; slices stay element ranges)
@@ -856,6 +860,10 @@ class GraphedTrainStep:
                     else:
                         for t in tables:
                             self.opt.launch_tables(t)
+            if hasattr(self.opt, "stats_setting") and self.opt.stats_setting():
+                # per-tensor statistics: once, behind the last update of the step on the stream the updates ran on
+                with torch.cuda.stream(self._comm_stream) if overlap else contextlib.nullcontext():
+                    self.opt.tensor_stats_launch()
             if overlap:
                 cur.wait_stream(self._comm_stream)
             self.opt.finish_group_step()

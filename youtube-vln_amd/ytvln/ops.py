@@ -2057,3 +2057,39 @@ def ema_swap(p: Tensor, e: Tensor, chunks: Tensor, nchunks: int, p_bf16: Optiona
     if e.numel() != p.numel() or (p_bf16 is not None and p_bf16.numel() != p.numel()):
         raise RuntimeError("ema_swap: the shadow arena and the bf16 copy must have the size of the parameter arena")
     call("ytvln_ema_swap", _ptr(p), _ptr(e), None if p_bf16 is None else p_bf16.data_ptr(), chunks.data_ptr(), int(nchunks), _stream())
+
+
+def _check_stats_partials(partials: Tensor, bad: Tensor, nchunks: int, who: str):
+    _check(partials, "partials")
+    if not bad.is_cuda or bad.dtype != torch.int32 or not bad.is_contiguous() or not partials.is_contiguous():
+        raise RuntimeError(f"{who}: partials must be contiguous float32 and bad contiguous int32 GPU tensors")
+    if partials.numel() < 4 * int(nchunks) or bad.numel() < 2 * int(nchunks):
+        raise RuntimeError(f"{who}: {int(nchunks)} records need four partials and two counts each")
+
+
+def tensor_stats_stage1(p: Tensor, g: Tensor, chunks: Tensor, nchunks: int, partials: Tensor, bad: Tensor):
+    """First pass of the per-tensor statistics (include/ytvln.h: ytvln_tensor_stats_stage1) over an AdamW chunk table, on the current stream:
+    partials[4i : 4i+4] = [sum g^2, max |g|, sum p^2, max |p|] over the finite elements of record i and bad[2i : 2i+2] = its non-finite
+    elements of g and of p.  `g`: the fp32 gradient arena or the bf16 exchange buffer.  Read-only for p and g."""
+    _check(p, "p")
+    dt = _grad_dtype(g)
+    _check(g, "g", g.dtype)
+    _check_stats_partials(partials, bad, nchunks, "tensor_stats_stage1")
+    call("ytvln_tensor_stats_stage1", _ptr(p), g.data_ptr(), dt, chunks.data_ptr(), int(nchunks), _ptr(partials), bad.data_ptr(), _stream())
+
+
+def tensor_stats_stage2(partials: Tensor, bad: Tensor, nchunks: int, tensor_first: Tensor, rec_tensor: Tensor, ntensors: int,
+                        grad_scale: float, stats: Tensor, counts: Tensor):
+    """stats[k] = [grad_scale * ||g||, grad_scale * max |g|, ||p||, max |p|] and counts[k] = [non-finite g, non-finite p, launches so far
+    with a non-finite g] for every tensor of a chunk table from the partials of tensor_stats_stage1 (include/ytvln.h:
+    ytvln_tensor_stats_stage2), on the current stream.  `tensor_first` / `rec_tensor` as for lamb_trust; stats (float32, four per row) and
+    counts (int64, three per row) are indexed by rec_tensor's values."""
+    _check(stats, "stats")
+    _check(counts, "counts", torch.int64)
+    _check_stats_partials(partials, bad, nchunks, "tensor_stats_stage2")
+    _check_i32(tensor_first, "tensor_first", int(ntensors) + 1)
+    _check_i32(rec_tensor, "rec_tensor", int(nchunks))
+    if not stats.is_contiguous() or not counts.is_contiguous() or stats.numel() % 4 or counts.numel() * 4 != stats.numel() * 3:
+        raise RuntimeError("tensor_stats_stage2: stats must hold four floats and counts three int64 per row, both contiguous")
+    call("ytvln_tensor_stats_stage2", _ptr(partials), bad.data_ptr(), tensor_first.data_ptr(), rec_tensor.data_ptr(), int(ntensors),
+         float(grad_scale), _ptr(stats), counts.data_ptr(), _stream())

@@ -9,8 +9,9 @@ arenas, and a whole step is one HIP kernel launch per (param-group, step-count) 
 tensor x 541 tensors.  The flat gradient arena is also what the data-parallel all-reduce buckets (ytvln/distributed.py).
 
 Beyond the reference (it has no gradient clipping): two plain attributes, `optimizer.max_grad_norm` and `optimizer.skip_nonfinite`, bound
-the global gradient norm inside the step, `optimizer.trust_ratio` switches the update to LAMB's layer-wise trust ratio, and
-`optimizer.ema_decay` keeps an exponential moving average of the weights in a shadow arena -- see the `AdamW` docstring.
+the global gradient norm inside the step, `optimizer.trust_ratio` switches the update to LAMB's layer-wise trust ratio,
+`optimizer.ema_decay` keeps an exponential moving average of the weights in a shadow arena, and `optimizer.tensor_stats` reports norms,
+maxima and non-finite counts per parameter tensor -- see the `AdamW` docstring.
 """
 from __future__ import annotations
 
@@ -163,7 +164,20 @@ class AdamW(Optimizer):
     shadow: nothing is exchanged.  `ema_parameters()` maps parameters to their shadow views, `ema_state_dict(model)` is the model file with
     the shadow weights, `swap_ema()` / `with optimizer.ema_weights():` exchange weights and shadow in place for evaluation (views, arena
     slots and captured graphs stay valid; stepping while swapped raises RuntimeError), `ema_checkpoint(model)` / `load_ema(state, model)`
-    carry the shadow through checkpoints (ytvln.utils_init.save_model, ytvln.vilbert_init.restore_checkpoint)."""
+    carry the shadow through checkpoints (ytvln.utils_init.save_model, ytvln.vilbert_init.restore_checkpoint).
+
+    tensor_stats (attribute, default False): True makes every step -- eager, while capturing, on replay -- report per parameter tensor what
+        the step did: behind the update launches (and the EMA launch) of the step, ytvln_tensor_stats_stage1 and ytvln_tensor_stats_stage2
+        run over every launch class's whole chunk table (8 bytes per parameter read, 6 with bf16 gradients; no host synchronisation, no
+        atomics, fixed summation orders).  `tensor_stats_report()` returns two device views in arena order: rows [||g||, max |g|, ||p||,
+        max |p|] over the finite elements and rows [non-finite elements of g, of p, steps so far with a non-finite g]; g is the gradient
+        the update read (after the exchange, the bf16 sums with the bf16 exchange, times grad_scale, unclipped -- the quantity grad_norm()
+        describes), p the parameter the next forward will use.  A step the device skipped (skip_nonfinite) leaves p unchanged and still
+        reports: `nonfinite_tensors(model)` names the tensors whose gradient went non-finite (it synchronises), `tensor_names(model)` the
+        rows.  A plain attribute like the others (anything but a bool raises ValueError when the step is taken), not in state_dict(); with
+        False a step launches and allocates exactly what it always did.  On / off is baked into a captured step (`prepare_replay()` raises
+        when it differs); its small buffers come from the first eager step with it on or from `stats_buffers()` and are dropped with the
+        arena, the sticky count with them."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
         if lr < 0.0:
@@ -190,6 +204,8 @@ class AdamW(Optimizer):
         self.ema_warmup = False
         self.ema_updates = 0        # EMA updates taken (host count; advances on a device-skipped step as state[p]["step"] does)
         self._captured_ema = None   # feature on / off as recorded into the last captured step (None: nothing captured yet)
+        self.tensor_stats = False   # per-tensor gradient / weight statistics (class docstring); a plain attribute, never part of state_dict()
+        self._captured_stats = None  # tensor_stats as recorded into the last captured step (None: nothing captured yet)
         self._ema_swapped = False   # swap_ema(): the parameter arena currently holds the shadow weights
         self._ema_carry = {}        # id(param) -> shadow values waiting for the next arena (rebuild, load_ema)
 
@@ -234,7 +250,7 @@ class AdamW(Optimizer):
                 st["exp_avg_sq"] = flat["v"][o:o + n].view(p.shape)
         self._stash_ema(old)
         self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None, partials=None, clip=None,
-                           lamb=None, ema=None)
+                           lamb=None, ema=None, stats=None)
         self._launch = None
         del old
         if self._ema_carry and self.ema_decay is not None and not torch.cuda.is_current_stream_capturing():
@@ -412,6 +428,68 @@ class AdamW(Optimizer):
         ops.lamb_trust(part, c["table"], c["n"], c["tensor_first"], c["rec_tensor"], c["ntensors"], trust, report, clip)
         ops.lamb_stage2(a["p"], a["m"], a["v"], c["table"], c["n"], c["hyper"], trust, c["rec_tensor"], clip, p_bf16=a["pb"])
         a["lamb_stepped"] = True
+
+    # ---- per-tensor gradient / weight statistics ----------------------------------------------------------------------
+    def stats_setting(self) -> bool:
+        """tensor_stats, validated: anything but a bool raises ValueError."""
+        if not isinstance(self.tensor_stats, bool):
+            raise ValueError(f"tensor_stats must be True or False, got {self.tensor_stats!r}")
+        return self.tensor_stats
+
+    def stats_buffers(self):
+        """(partials, bad, stats, counts): four fp32 partials and two int32 counts per CHUNK record of the arena, one report row
+        [grad norm, max |g|, weight norm, max |p|] (fp32) and one row [non-finite g, non-finite p, steps with a non-finite g] (int64) per
+        arena tensor.  Allocated on first use -- only with tensor_stats on -- and dropped with the arena (the sticky third count restarts
+        with it, as skipped_steps() does); not part of state_dict.  None before the arena exists."""
+        a = self._arena
+        if a is None:
+            return None
+        if a["stats"] is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("tensor_stats was switched on after the last eager step: take one eager step with it on (or call "
+                                   "stats_buffers()) before capturing, so that its buffers do not live in a graph's pool")
+            dev, nt = a["g"].device, len(a["index"])
+            n = sum((numel + CHUNK - 1) // CHUNK for _, numel in a["index"].values())
+            a["stats"] = (torch.zeros(4 * n, dtype=torch.float32, device=dev), torch.zeros(2 * n, dtype=torch.int32, device=dev),
+                          torch.zeros(nt, 4, dtype=torch.float32, device=dev), torch.zeros(nt, 3, dtype=torch.int64, device=dev))
+            a["stats_stepped"] = False
+        return a["stats"]
+
+    def tensor_stats_launch(self):
+        """The two statistics launches of every launch class over its whole chunk table, on the current stream.  Belongs behind the step's
+        update (and EMA) launches: g is then the gradient the update read -- the updates never write it --, p the parameter it wrote."""
+        a = self._arena
+        partials, bad, stats, counts = self.stats_buffers()
+        g = self._grad_operand()
+        for c in self._launch:
+            part, cnt = partials[4 * c["rec0"]:4 * (c["rec0"] + c["n"])], bad[2 * c["rec0"]:2 * (c["rec0"] + c["n"])]
+            ops.tensor_stats_stage1(a["p"], g, c["table"], c["n"], part, cnt)
+            ops.tensor_stats_stage2(part, cnt, c["n"], c["tensor_first"], c["rec_tensor"], c["ntensors"], self.grad_scale, stats, counts)
+        a["stats_stepped"] = True
+
+    def tensor_stats_report(self):
+        """(stats [tensors in arena order (arena_layout(), tensor_names()), 4] fp32, counts [same rows, 3] int64) of the last step with
+        tensor_stats on: stats rows are [||g||, max |g|, ||p||, max |p|] over the finite elements, g being the gradient the update read
+        (after the exchange, unclipped, times grad_scale: what grad_norm() describes) and p the parameter after the step; counts rows are
+        [non-finite elements of g, of p, steps so far with a non-finite g].  Device views -- no synchronisation; later steps overwrite them."""
+        a = self._arena
+        if a is None or a["stats"] is None or not a["stats_stepped"]:
+            raise RuntimeError("tensor_stats_report(): no step has been taken with tensor_stats = True")
+        return a["stats"][2], a["stats"][3]
+
+    def tensor_names(self, model) -> List:
+        """The names of `model.named_parameters()` in arena order: the rows of tensor_stats_report() and trust_ratios().  A tied parameter
+        carries its first name; a member that `model` does not hold gets None."""
+        if self._arena is None:
+            raise RuntimeError("tensor_names(): no step has been taken yet: the arena does not exist")
+        names = {id(p): n for n, p in model.named_parameters()}
+        return [names.get(pid) for pid in self._arena["index"]]
+
+    def nonfinite_tensors(self, model) -> Dict[str, tuple]:
+        """{parameter name: (non-finite gradient elements in the last step, steps so far with a non-finite gradient)} for every arena
+        tensor whose gradient has been non-finite at least once since the arenas were built.  Reads the device counts: SYNCHRONISES."""
+        counts = self.tensor_stats_report()[1].cpu()
+        return {name: (int(row[0]), int(row[2])) for name, row in zip(self.tensor_names(model), counts) if int(row[2]) > 0}
 
     # ---- EMA of the weights --------------------------------------------------------------------------------------------
     def ema_setting(self):
@@ -699,7 +777,10 @@ class AdamW(Optimizer):
             self._captured_clip = self.clip_settings()
             self._captured_lamb = self.lamb_setting()
             self._captured_ema = self.ema_setting() is not None
+            self._captured_stats = self.stats_setting()
         self.launch_classes()
+        if self.stats_setting():                  # behind every update and EMA launch of the step
+            self.tensor_stats_launch()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -710,6 +791,7 @@ class AdamW(Optimizer):
         self.clip_settings()              # invalid max_grad_norm: ValueError before anything is exchanged, launched or recorded
         self.lamb_setting()               # (and an invalid trust_ratio)
         self.ema_setting()                # (and an invalid ema_decay / ema_warmup)
+        self.stats_setting()              # (and an invalid tensor_stats)
         self._not_swapped("step()")
         if torch.cuda.is_current_stream_capturing():
             # inside a hipGraph capture of a whole training step: only the device work is recorded; the caller uploads the
@@ -840,8 +922,8 @@ class AdamW(Optimizer):
 
     def prepare_replay(self):
         """Call before each replay of a captured training step (after scheduler.step() set the new learning rate).  The captured step
-        carries the clipping settings, trust_ratio and EMA on / off it was recorded with: raises if one of them changed since (the EMA's
-        decay and warm-up travel by value and may change freely)."""
+        carries the clipping settings, trust_ratio, EMA on / off and tensor_stats it was recorded with: raises if one of them changed since
+        (the EMA's decay and warm-up travel by value and may change freely)."""
         self._not_swapped("prepare_replay()")
         if self._captured_clip is not False and self.clip_settings() != self._captured_clip:
             raise RuntimeError(f"max_grad_norm / skip_nonfinite changed since the step was captured (captured {self._captured_clip}, now "
@@ -851,6 +933,9 @@ class AdamW(Optimizer):
                                "the graph holds the old launches -- capture the step again")
         if self._captured_ema is not None and (self.ema_setting() is not None) != self._captured_ema:
             raise RuntimeError(f"ema_decay was switched {'off' if self._captured_ema else 'on'} since the step was captured: "
+                               "the graph holds the old launches -- capture the step again")
+        if self._captured_stats is not None and self.stats_setting() != self._captured_stats:
+            raise RuntimeError(f"tensor_stats changed since the step was captured (captured {self._captured_stats}, now {self.tensor_stats}): "
                                "the graph holds the old launches -- capture the step again")
         self._upload_hyper()
 

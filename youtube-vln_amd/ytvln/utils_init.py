@@ -194,7 +194,8 @@ def train_step(model, optimizer, scheduler, batch, args, step: int = 0, logger=N
                loss_aware_heads: bool = False, capacity_frac: float = 0.25, optimizer_step: bool = True, backward=None):
     """One iteration of train_epoch's body (utils_init.py:199-239): forward, loss composition in the reference's order,
     backward, and -- every gradient_accumulation_steps -- optimizer.step(); scheduler.step(); zero_grad().
-    Returns (loss, reduced_metrics) as device tensors; never synchronises the host.
+    Returns (loss, reduced_metrics) as device tensors; never synchronises the host.  With `optimizer.tensor_stats` on, a micro-step that
+    takes the optimizer step adds reduced_metrics["nonfinite_grad_tensors"]: the number of arena tensors whose gradient was non-finite.
     `backward` (optional callable taking the loss) replaces `loss.backward()` -- ytvln.distributed.GraphedTrainStep runs the backward
     pass in phases through it."""
     reduced_metrics = {"loss": {}, "accuracy": {}}
@@ -234,6 +235,9 @@ def train_step(model, optimizer, scheduler, batch, args, step: int = 0, logger=N
         return loss.detach(), reduced_metrics
     if (step + 1) % accum == 0:
         optimizer.step()
+        if getattr(optimizer, "tensor_stats", False) is True:
+            # device scalar; > 0 means this step read a non-finite gradient: optimizer.nonfinite_tensors(model) names the tensors
+            reduced_metrics["nonfinite_grad_tensors"] = (optimizer.tensor_stats_report()[1][:, 0] > 0).sum().float()
         if scheduler is not None:
             scheduler.step()
         if hasattr(optimizer, "_arena"):

@@ -75,6 +75,8 @@ def get_optimization(args, model, train_data_loader_length, logger):
         optimizer.ema_decay = args.ema_decay
     if hasattr(args, "ema_warmup"):
         optimizer.ema_warmup = args.ema_warmup
+    if hasattr(args, "tensor_stats"):         # per-tensor gradient / weight statistics (beyond the reference as well); validated when a step is taken
+        optimizer.tensor_stats = args.tensor_stats
     scheduler = build_scheduler(args, optimizer, train_data_loader_length)
     start_epoch = 0
     if getattr(args, "resume", False):
