@@ -446,6 +446,40 @@ int ytvln_kl_fwd_bf16(const uint16_t* pred, int64_t ld, const float* target, int
 int ytvln_kl_bwd_bf16(const uint16_t* pred, int64_t ld, const float* target, int64_t ldt, const int64_t* mask, const float* row_lse,
                       const float* out, const float* gout, uint16_t* dpred, int64_t ldd, int M, int C, void* stream);
 
+/* ---- stats forms of the two losses above: label smoothing and the row arg-max from the same pass (opt-in; fp32 or bf16 logits) ----------
+ * ytvln_ce_stats_fwd_*: one workgroup per non-ignored row streams the row ONCE for the log-sum-exp (the bits of ytvln_ce_fwd_*), sx = the
+ * sum and nv = the number of its logits that are not -inf, and the arg-max.  Two launches, no atomics, deterministic.
+ *   row loss  = (1 - eps) (lse - x[t]) + eps (lse - sx / nv),  eps = label_smoothing in [0, 1)
+ *               = F.cross_entropy(label_smoothing = eps) when no logit is -inf; with -inf logits (padded ranking options) the smoothing
+ *               mass is spread over the nv other classes only, where torch spreads it over all V and returns +inf.  eps = 0: the bits of
+ *               ytvln_ce_fwd_*.  A -inf TARGET logit gives +inf; a target outside [0, V) that is not the ignore index, or a NaN logit, NaN.
+ *   row_top[r] = arg-max of row r: the LOWEST index among equal maxima, a NaN counts as the maximum (torch.argmax); -1 for an ignored row
+ *   row_aux[r] = nv (read by the backward);  row_lse, row_loss: as ytvln_ce_fwd_*
+ *   out[0] = mean loss over the non-ignored rows (NaN when none), out[1] = their count, out[2] = hits = #(non-ignored rows with
+ *   row_top == target), out[3] = rows counted = out[1].  hits and counts are whole numbers in fp32: M <= 2^24.
+ * ytvln_ce_smooth_bwd_*: dlogits[c] = (p_c - (1 - eps) [c == t] - (eps / nv) [x_c != -inf]) * gout[0] / count, p = softmax; a -inf column
+ * gets p_c = 0 and no smoothing term.  Stores as ytvln_ce_bwd_*: fp32 into columns [0, V); bf16 rounded once, zeros up to ldd.  `out` is
+ * the forward's.  With eps = 0 it writes what ytvln_ce_bwd_* writes.
+ * ytvln_kl_stats_fwd_*: ytvln_kl_fwd_* (same row_lse, row_loss, out[0], out[1] -- ytvln_kl_bwd_* is its backward) plus row_top[r] = arg-max
+ * of the prediction row (-1 where mask == 0), row_hit[r] = 1 where it equals the arg-max of the target row (same tie rule) and mask != 0,
+ * out[2] = sum(row_hit), out[3] = #(mask != 0), not clamped.
+ * All of them: ld (ldt, ldd) >= V; the columns beyond V are never read.  Bad arguments (null pointer, M outside 1 .. 2^24, a leading
+ * dimension below V, label_smoothing outside [0, 1) or NaN) return a negative code before anything is launched. */
+int ytvln_ce_stats_fwd_f32(const float* logits, int64_t ld, const int64_t* target, int64_t ignore_index, float label_smoothing,
+                           float* row_lse, float* row_aux, float* row_loss, int64_t* row_top, float* out, int M, int V, void* stream);
+int ytvln_ce_stats_fwd_bf16(const uint16_t* logits, int64_t ld, const int64_t* target, int64_t ignore_index, float label_smoothing,
+                            float* row_lse, float* row_aux, float* row_loss, int64_t* row_top, float* out, int M, int V, void* stream);
+int ytvln_ce_smooth_bwd_f32(const float* logits, int64_t ld, const int64_t* target, int64_t ignore_index, float label_smoothing,
+                            const float* row_lse, const float* row_aux, const float* out, const float* gout, float* dlogits, int64_t ldd,
+                            int M, int V, void* stream);
+int ytvln_ce_smooth_bwd_bf16(const uint16_t* logits, int64_t ld, const int64_t* target, int64_t ignore_index, float label_smoothing,
+                             const float* row_lse, const float* row_aux, const float* out, const float* gout, uint16_t* dlogits, int64_t ldd,
+                             int M, int V, void* stream);
+int ytvln_kl_stats_fwd_f32(const float* pred, int64_t ld, const float* target, int64_t ldt, const int64_t* mask, float* row_lse,
+                           float* row_loss, int64_t* row_top, float* row_hit, float* out, int M, int C, void* stream);
+int ytvln_kl_stats_fwd_bf16(const uint16_t* pred, int64_t ld, const float* target, int64_t ldt, const int64_t* mask, float* row_lse,
+                            float* row_loss, int64_t* row_top, float* row_hit, float* out, int M, int C, void* stream);
+
 /* F.binary_cross_entropy_with_logits(x, t, pos_weight) with mean reduction (utils_init.py:143, 160-161). n <= 65536.
  * pos_weight is a DEVICE scalar or NULL.  bwd writes dx. */
 int ytvln_bce_fwd_f32(const float* x, const float* t, const float* pos_weight, float* out, int n, void* stream);

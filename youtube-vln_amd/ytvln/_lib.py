@@ -132,6 +132,13 @@ SIGNATURES = {
     "ytvln_ce_bwd_f32": [P, I64, P, I64, P, P, P, P, I64, I32, I32, P],
     "ytvln_kl_fwd_f32": [P, I64, P, I64, P, P, P, P, I32, I32, P],
     "ytvln_kl_bwd_f32": [P, I64, P, I64, P, P, P, P, P, I64, I32, I32, P],
+    # stats forms: label smoothing + the row arg-max from the same pass (csrc/loss.hip)
+    "ytvln_ce_stats_fwd_f32": [P, I64, P, I64, F32, P, P, P, P, P, I32, I32, P],
+    "ytvln_ce_stats_fwd_bf16": [P, I64, P, I64, F32, P, P, P, P, P, I32, I32, P],
+    "ytvln_ce_smooth_bwd_f32": [P, I64, P, I64, F32, P, P, P, P, P, I64, I32, I32, P],
+    "ytvln_ce_smooth_bwd_bf16": [P, I64, P, I64, F32, P, P, P, P, P, I64, I32, I32, P],
+    "ytvln_kl_stats_fwd_f32": [P, I64, P, I64, P, P, P, P, P, P, I32, I32, P],
+    "ytvln_kl_stats_fwd_bf16": [P, I64, P, I64, P, P, P, P, P, P, I32, I32, P],
     "ytvln_bce_fwd_f32": [P, P, P, P, I32, P],
     "ytvln_bce_bwd_f32": [P, P, P, P, P, I32, P],
     # losses of the downstream tasks (csrc/task_loss.hip)

@@ -1787,8 +1787,77 @@ class CrossEntropyFn(torch.autograd.Function):
         return _view_rows_as(dl, ldd, shape), None, None
 
 
-def cross_entropy(logits: Tensor, target: Tensor, ignore_index: int = -100) -> Tensor:
-    return CrossEntropyFn.apply(logits, target, ignore_index)
+def _label_smoothing(value) -> float:
+    """`label_smoothing` as a float in [0, 1), or ValueError (before anything is launched)."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 <= float(value) < 1.0:       # a NaN fails both comparisons
+        raise ValueError(f"label_smoothing must be a real number in [0, 1), got {value!r}")
+    return float(value)
+
+
+class CrossEntropyStatsFn(torch.autograd.Function):
+    """CrossEntropyFn with label smoothing and, from the same pass over the logits, the row arg-max, the hits and the row count."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, eps):
+        ctx.set_materialize_grads(False)
+        bf = logits.dtype == _BF16
+        lg, M, V, ld = _format_of(logits).rows(logits, "logits")
+        tg = _i64(target, "target").reshape(-1)
+        assert tg.numel() == M, (tg.shape, M)
+        dev = lg.device
+        row_lse = torch.empty(M, dtype=torch.float32, device=dev)
+        row_nv = torch.empty(M, dtype=torch.float32, device=dev)
+        row_loss = torch.empty(M, dtype=torch.float32, device=dev)
+        row_top = torch.empty(M, dtype=torch.int64, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        call("ytvln_ce_stats_fwd_bf16" if bf else "ytvln_ce_stats_fwd_f32", lg.data_ptr(), ld, _ptr(tg), int(ignore_index), eps, _ptr(row_lse),
+             _ptr(row_nv), _ptr(row_loss), row_top.data_ptr(), _ptr(out), M, V, _stream())
+        ctx.meta = (M, V, ld, int(ignore_index), eps, logits.shape)
+        ctx.bf16_grad = bf
+        ctx.save_for_backward(lg, tg, row_lse, row_nv, out)
+        loss, hits, count = out[0], out[2], out[3]
+        ctx.mark_non_differentiable(hits, count, row_top)
+        return loss, hits, count, row_top
+
+    @staticmethod
+    def backward(ctx, g, _ghits=None, _gcount=None, _gtop=None):
+        if g is None:
+            return None, None, None, None
+        lg, tg, row_lse, row_nv, out = ctx.saved_tensors
+        M, V, ld, ign, eps, shape = ctx.meta
+        g = g.reshape(1).contiguous().float()
+        sfx = "bf16" if ctx.bf16_grad else "f32"
+        if ctx.bf16_grad:
+            dl, ldd = _alloc_rows_bf16(M, V, lg.device)
+        else:
+            dl, ldd = _F32.alloc_rows(M, V, lg.device, zero_pad=True)
+        if eps == 0.0:          # no smoothing: the plain backward as it stands
+            call("ytvln_ce_bwd_" + sfx, lg.data_ptr(), ld, _ptr(tg), ign, _ptr(row_lse), _ptr(out), _ptr(g), dl.data_ptr(), ldd, M, V, _stream())
+        else:
+            call("ytvln_ce_smooth_bwd_" + sfx, lg.data_ptr(), ld, _ptr(tg), ign, eps, _ptr(row_lse), _ptr(row_nv), _ptr(out), _ptr(g),
+                 dl.data_ptr(), ldd, M, V, _stream())
+        return _view_rows_as(dl, ldd, shape), None, None, None
+
+
+def cross_entropy(logits: Tensor, target: Tensor, ignore_index: int = -100, label_smoothing: float = 0.0) -> Tensor:
+    """F.cross_entropy(logits, target, ignore_index=ignore_index, label_smoothing=label_smoothing), mean reduction.  With smoothing, -inf
+    logits (padded options) take no share of the smoothing mass: see cross_entropy_stats."""
+    eps = _label_smoothing(label_smoothing)
+    if eps == 0.0:
+        return CrossEntropyFn.apply(logits, target, ignore_index)
+    return CrossEntropyStatsFn.apply(logits, target, ignore_index, eps)[0]
+
+
+def cross_entropy_stats(logits: Tensor, target: Tensor, ignore_index: int = -100,
+                        label_smoothing: float = 0.0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(loss, hits, count, row_top) from one pass over the logits, without a host sync:
+    loss = the label-smoothed cross entropy, mean over the rows whose target is not `ignore_index` (0-d, differentiable in `logits`; NaN when
+    there is no such row).  Row loss = (1 - eps)(lse - x[t]) + eps (lse - mean of the row's logits that are not -inf): F.cross_entropy's value
+    when no logit is -inf; with -inf logits the smoothing mass goes to the other classes only (torch gives +inf there), and the gradient of a
+    -inf column is 0.  With label_smoothing = 0 the loss and its gradient are cross_entropy's, bit for bit.
+    row_top = int64 [M], the arg-max of each row: lowest index among equals, a NaN counts as the maximum (torch.argmax); -1 for an ignored row.
+    hits = number of non-ignored rows with row_top == target, count = number of non-ignored rows (0-d fp32, exact up to 2^24 rows)."""
+    return CrossEntropyStatsFn.apply(logits, target, ignore_index, _label_smoothing(label_smoothing))
 
 
 class KLMaskedFn(torch.autograd.Function):
@@ -1831,6 +1900,44 @@ class KLMaskedFn(torch.autograd.Function):
 
 def kl_masked(pred: Tensor, target: Tensor, mask: Tensor) -> Tensor:
     return KLMaskedFn.apply(pred, target, mask)
+
+
+class KLMaskedStatsFn(torch.autograd.Function):
+    """KLMaskedFn plus, from the same pass, the arg-max of every prediction row and how many of them agree with the target row's."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask):
+        ctx.set_materialize_grads(False)
+        bf = pred.dtype == _BF16
+        pr, M, Cc, ld = _format_of(pred).rows(pred, "pred")
+        tg, M2, C2, ldt = _F32.rows(target, "target")
+        assert (M, Cc) == (M2, C2), (pred.shape, target.shape)
+        mk = _i64(mask, "mask").reshape(-1)
+        dev = pr.device
+        row_lse = torch.empty(M, dtype=torch.float32, device=dev)
+        row_loss = torch.empty(M, dtype=torch.float32, device=dev)
+        row_hit = torch.empty(M, dtype=torch.float32, device=dev)
+        row_top = torch.empty(M, dtype=torch.int64, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        call("ytvln_kl_stats_fwd_bf16" if bf else "ytvln_kl_stats_fwd_f32", pr.data_ptr(), ld, _ptr(tg), ldt, _ptr(mk), _ptr(row_lse),
+             _ptr(row_loss), row_top.data_ptr(), _ptr(row_hit), _ptr(out), M, Cc, _stream())
+        ctx.meta = (M, Cc, ld, ldt, pred.shape)
+        ctx.bf16_grad = bf
+        ctx.save_for_backward(pr, tg, mk, row_lse, out)
+        loss, hits, count = out[0], out[2], out[3]
+        ctx.mark_non_differentiable(hits, count, row_top)
+        return loss, hits, count, row_top
+
+    @staticmethod
+    def backward(ctx, g, _ghits=None, _gcount=None, _gtop=None):          # ytvln_kl_bwd_* reads out[1] only: the plain backward serves
+        return KLMaskedFn.backward(ctx, g)
+
+
+def kl_masked_stats(pred: Tensor, target: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(loss, hits, count, row_top): kl_masked's loss (same bits, same gradient) and, from the same pass, row_top = int64 [M] arg-max of each
+    prediction row (lowest index among equals, a NaN counts as the maximum; -1 where mask == 0), hits = number of rows with mask != 0 whose
+    arg-max equals the target row's, count = number of rows with mask != 0 (0-d fp32, not clamped).  No host sync."""
+    return KLMaskedStatsFn.apply(pred, target, mask)
 
 
 class BCEWithLogitsFn(torch.autograd.Function):

@@ -85,9 +85,26 @@ def get_linguistic_target(batch, all_options=False):
     return batch[8][get_mask_options(batch)].flatten()
 
 
+def loss_settings(args):
+    """(label_smoothing, token_accuracy) of an args object, both optional and off by default, checked every time a step reads them.
+    `args.label_smoothing` (a number in [0, 1)) smooths the `language` cross entropy and the TRAINING `ranking` cross entropy, nothing else.
+    `args.token_accuracy` (a bool) adds reduced_metrics["accuracy"]["language"] (hits / target-carrying tokens) and ["vision"] (hits / masked
+    regions; a hit = the arg-max of the prediction equals the arg-max of the target distribution), both from the pass of the loss kernel
+    that reads the logits anyway."""
+    eps = getattr(args, "label_smoothing", 0.0)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= float(eps) < 1.0:      # a NaN fails both comparisons
+        raise ValueError(f"args.label_smoothing must be a real number in [0, 1), got {eps!r}")
+    token_accuracy = getattr(args, "token_accuracy", False)
+    if not isinstance(token_accuracy, bool):
+        raise ValueError(f"args.token_accuracy must be a bool, got {token_accuracy!r}")
+    return float(eps), token_accuracy
+
+
 def get_loss_correct(batch: List[torch.Tensor], outputs: Dict[str, torch.Tensor], task, args, logger, training,
                      all_options=False):
-    """utils_init.py:108-164 -> (batch_size, target, loss, correct).  `all_options`: see get_model_input."""
+    """utils_init.py:108-164 -> (batch_size, target, loss, correct).  `all_options`: see get_model_input.
+    With args.token_accuracy the `vision` and `language` tasks return (rows counted, target, loss, hits), the first a device scalar."""
+    eps, token_accuracy = loss_settings(args)
     opt_mask = get_mask_options(batch)
     unpack = (lambda t: t.view(opt_mask.shape)) if all_options else (lambda t: pad_packed(t, opt_mask))
     batch_size = get_batch_size(batch)
@@ -97,15 +114,23 @@ def get_loss_correct(batch: List[torch.Tensor], outputs: Dict[str, torch.Tensor]
         predictions = outputs["vision"]
         predictions = predictions.reshape(-1, predictions.shape[2])
         target, target_mask = get_vision_target(batch, all_options)
-        loss = ops.kl_masked(predictions, target.float(), target_mask)        # sum(KL*mask) / max(1, sum(mask)), on device
+        if token_accuracy:
+            loss, correct, batch_size, _ = ops.kl_masked_stats(predictions, target.float(), target_mask)
+        else:
+            loss = ops.kl_masked(predictions, target.float(), target_mask)        # sum(KL*mask) / max(1, sum(mask)), on device
     elif task == "language":
         voc_size = outputs["language"].shape[-1]
         target = get_linguistic_target(batch, all_options)
-        loss = ops.cross_entropy(outputs["language"].reshape(-1, voc_size), target, ignore_index=-1)
+        if token_accuracy:
+            loss, correct, batch_size, _ = ops.cross_entropy_stats(outputs["language"].reshape(-1, voc_size), target, -1, eps)
+        else:
+            loss = ops.cross_entropy(outputs["language"].reshape(-1, voc_size), target, ignore_index=-1, label_smoothing=eps)
     elif task == "ranking":
         target = get_ranking_target(batch)
         prediction = unpack(outputs["ranking"].squeeze(1))
-        if training:
+        if training and (eps != 0.0 or token_accuracy):      # hits = rows whose row_top is the target: the arg-max rides in the loss kernel
+            loss, correct, _, _ = ops.cross_entropy_stats(prediction, target, -1, eps)
+        elif training:
             loss = ops.cross_entropy(prediction, target, ignore_index=-1)
             correct = torch.sum(torch.argmax(prediction, 1) == target).float()
         else:
@@ -134,7 +159,10 @@ def compute_metrics_independent(batch, outputs, task, args, logger, reduced_metr
     batch_size, target, loss, correct = get_loss_correct(batch, outputs, task, args, logger, True, all_options)
     reduced_loss = loss.detach().float()
     reduced_correct = correct.detach().float()
-    reduced_batch_size = torch.full((), float(batch_size), device=device)
+    if torch.is_tensor(batch_size):       # token_accuracy: the rows the stats kernel counted, already on the device
+        reduced_batch_size = batch_size.detach().float()
+    else:
+        reduced_batch_size = torch.full((), float(batch_size), device=device)
     if getattr(args, "local_rank", -1) != -1 and not getattr(args, "skip_all_reduce", False) and dist.is_initialized():
         from . import distributed as D
         packed = torch.stack([reduced_loss / float(D.metrics_world_size()), reduced_correct, reduced_batch_size])
@@ -143,6 +171,8 @@ def compute_metrics_independent(batch, outputs, task, args, logger, reduced_metr
     reduced_metrics["loss"][task] = reduced_loss
     if task not in ("vision", "language"):
         reduced_metrics["accuracy"][task] = reduced_correct / reduced_batch_size
+    elif loss_settings(args)[1]:
+        reduced_metrics["accuracy"][task] = reduced_correct / reduced_batch_size.clamp(min=1.0)
     return loss
 
 
@@ -158,6 +188,7 @@ def _loss_aware_step(model, batch, args, all_options, capacity_frac):
     """Forward + losses with the prediction heads evaluated only on rows that carry a target.  Identical
     losses and gradients: ignored tokens / unmasked regions contribute nothing to CE / KL.  Row selection has a static shape
     (`capacity_frac` of the rows; Bernoulli(0.15) masking makes 0.25 a > 20 sigma bound) and needs no host sync."""
+    eps, token_accuracy = loss_settings(args)
     inputs = get_model_input(batch, all_options)
     rows, lm_t, vis_t, vis_m = {}, None, None, None
     if args.masked_language:
@@ -169,15 +200,23 @@ def _loss_aware_step(model, batch, args, all_options, capacity_frac):
         cap = _head_capacity(vis_m.numel(), capacity_frac)
         rows["vision"] = ops.select_rows(vis_m == 1, cap)
     outputs = model(*inputs, head_rows=rows)
-    losses = {}
+    losses, accuracy = {}, {}
     if args.masked_vision:
         idx = rows["vision"]
-        losses["vision"] = ops.kl_masked(outputs["vision"], ops.gather_rows(vis_t.float(), idx), vis_m[idx])
+        if token_accuracy:
+            losses["vision"], hits, count, _ = ops.kl_masked_stats(outputs["vision"], ops.gather_rows(vis_t.float(), idx), vis_m[idx])
+            accuracy["vision"] = hits / count.clamp(min=1.0)
+        else:
+            losses["vision"] = ops.kl_masked(outputs["vision"], ops.gather_rows(vis_t.float(), idx), vis_m[idx])
     if args.masked_language:
-        losses["language"] = ops.cross_entropy(outputs["language"], lm_t[rows["language"]], ignore_index=-1)
+        if token_accuracy:
+            losses["language"], hits, count, _ = ops.cross_entropy_stats(outputs["language"], lm_t[rows["language"]], -1, eps)
+            accuracy["language"] = hits / count.clamp(min=1.0)
+        else:
+            losses["language"] = ops.cross_entropy(outputs["language"], lm_t[rows["language"]], ignore_index=-1, label_smoothing=eps)
     overflow = sum(((t != ign).sum() > r.numel()).float() for t, ign, r in
                    ((lm_t, -1, rows.get("language")), (vis_m, 0, rows.get("vision"))) if t is not None)
-    return outputs, losses, overflow
+    return outputs, losses, accuracy, overflow
 
 
 def padding_row_overflow(model):
@@ -199,9 +238,11 @@ def train_step(model, optimizer, scheduler, batch, args, step: int = 0, logger=N
     `backward` (optional callable taking the loss) replaces `loss.backward()` -- ytvln.distributed.GraphedTrainStep runs the backward
     pass in phases through it."""
     reduced_metrics = {"loss": {}, "accuracy": {}}
+    loss_settings(args)          # an invalid label_smoothing / token_accuracy: ValueError before anything is launched
     fused = {}
     if loss_aware_heads and (args.masked_language or args.masked_vision):
-        outputs, fused, overflow = _loss_aware_step(model, batch, args, all_options, capacity_frac)
+        outputs, fused, accuracy, overflow = _loss_aware_step(model, batch, args, all_options, capacity_frac)
+        reduced_metrics["accuracy"].update(accuracy)
         reduced_metrics["head_row_overflow"] = overflow        # device scalar; > 0 means capacity_frac was too small
     else:
         outputs = model(*get_model_input(batch, all_options))
