@@ -178,10 +178,26 @@ int ytvln_cast_f32_bf16(const float* x, int64_t ldx, int64_t rows, int cols, uin
  *   ytvln_randomize_regions = randomize_regions (common.py:272-300):  p >= 0.85: targets = probs, targets_mask = 1 (else 1/C, 0);
  *     p >= 0.865: the feature row is zeroed IN PLACE.
  *   Draws: explicit (`p`, `random_tokens`; pins the kernels bit-for-bit to the reference functions) or, when those are NULL, the
- *   Philox stream keyed by the device-resident (seed, counter) pair `rng` and `site` (the same state as the dropout kernels). */
+ *   Philox stream keyed by the device-resident (seed, counter) pair `rng` and `site` (the same state as the dropout kernels).
+ *   ytvln_randomize_tokens_action = randomize_tokens with mask_action_rate > 0 (common.py:234-253).  tokens / mask / outputs are
+ *     [items, group]: `group` = K*T contiguous tokens of ONE dataset item, 1 <= group <= 8192.  Per item the positions of action0 (row-major),
+ *     then of action1, then of action2 are numbered 0..n-1, m = (int64)(rate * (double)n) ordinals are drawn WITH replacement and every drawn
+ *     position becomes [MASK] and a target, whatever its p and mask; all other positions follow ytvln_randomize_tokens.  A position drawn more
+ *     than once gets target = mask_token_id when repeat_target = 1 (what the reference computes: it reads back the [MASK] it has just
+ *     written) or the word when repeat_target = 0.  rate_bits = the IEEE-754 bits of the rate as a double (Python: struct '<q' of '<d'),
+ *     0 <= rate <= 16; rate 0 computes exactly ytvln_randomize_tokens.  counts (may be NULL): int64 [items, 2] = (n, m).
+ *     Draws: explicit (`p`, `random_tokens` and `action_choice` int64 [items, cap]: the first min(m, cap) entries of a row are read, values
+ *     outside [0, n) are skipped; action_choice may be NULL when cap = 0) or, when p / random_tokens are NULL, Philox: the per-token draws of
+ *     `site` exactly as ytvln_randomize_tokens lays them out, the ordinals from `action_site` (counter layout: csrc/batch.hip).
+ *     One workgroup per item, no global atomics, no host read, deterministic. */
 int ytvln_randomize_tokens(const int64_t* tokens, const int64_t* mask, int64_t n, int vocab_size, int64_t mask_token_id,
                            const float* p, const int64_t* random_tokens, const int64_t* rng, int64_t site,
                            int64_t* tokens_out, int64_t* targets_out, void* stream);
+int ytvln_randomize_tokens_action(const int64_t* tokens, const int64_t* mask, int64_t items, int64_t group, int vocab_size,
+                                  int64_t mask_token_id, int64_t action0, int64_t action1, int64_t action2, int64_t rate_bits,
+                                  int repeat_target, const float* p, const int64_t* random_tokens, const int64_t* action_choice,
+                                  int64_t cap, const int64_t* rng, int64_t site, int64_t action_site, int64_t* tokens_out,
+                                  int64_t* targets_out, int64_t* counts, void* stream);
 int ytvln_randomize_regions(float* features, int64_t ldf, const float* probs, const int64_t* mask, int64_t rows, int F, int C,
                             const float* p, const int64_t* rng, int64_t site, float* targets, int64_t* targets_mask, void* stream);
 
