@@ -201,6 +201,33 @@ int ytvln_randomize_tokens_action(const int64_t* tokens, const int64_t* mask, in
 int ytvln_randomize_regions(float* features, int64_t ldf, const float* probs, const int64_t* mask, int64_t rows, int F, int C,
                             const float* p, const int64_t* rng, int64_t site, float* targets, int64_t* targets_mask, void* stream);
 
+/* Ragged frame pool -> the padded tensors of a step, option expansion included, in one launch (csrc/pool.hip).  The pool holds the real
+ * rows of every distinct frame once, frame p in rows offsets[p] .. offsets[p+1]-1 (what the feature readers return, un-padded);
+ * `index` names the pool frame shown by each slot = (item, option, position), -1 = padding frame; position f = slot % frames.
+ * For slot s, box j in [0, boxes), p = index[s]:
+ *   n = min(offsets[p+1] - offsets[p], boxes) when 0 <= p < pool_frames and 0 <= offsets[p] <= offsets[p+1] <= pool_rows, else n = 0;
+ *   a p >= pool_frames, a p < -1 or such a pair of offsets out of order / out of range is a BAD slot: bad[0] += 1 when `bad` is given.
+ *   The range check on p comes before any read of offsets, the check of the offsets before any read of a row: nothing outside rows
+ *   [0, pool_rows) of the pool is read whatever index and offsets hold.
+ *   j <  n: the feature and probs rows are copies of pool row offsets[p] + j, out_boxes[:, :L] of pool_loc, columns L..10 = 0, mask 1;
+ *   j >= n: exact zeros, mask 0 (the outputs may hold anything on entry: every element is written);
+ *   out_boxes[:, 11] = f for EVERY row of every slot, padding frames included (all_dataset.py:314 and :331).
+ * No allocation, no host synchronisation, no atomics but the `bad` counter; capturable.  Null required pointers, negative sizes,
+ * frames <= 0, slots % frames != 0, L > 11 or only one of pool_probs / out_probs given return a negative code and launch nothing. */
+int ytvln_expand_ragged_f32(const float* pool_features,   /* [pool_rows, F]                                   */
+                            const float* pool_loc,        /* [pool_rows, L], L <= 11                          */
+                            const float* pool_probs,      /* [pool_rows, C] or NULL (then out_probs NULL too) */
+                            const int64_t* offsets,       /* [pool_frames + 1], first row of each frame       */
+                            int64_t pool_frames, int64_t pool_rows,
+                            const int64_t* index,         /* [slots] pool frame per (item, option, position), -1 = padding */
+                            int64_t slots, int frames, int boxes, int F, int L, int C,
+                            float* out_features,          /* [slots * boxes, F]  */
+                            float* out_boxes,             /* [slots * boxes, 12] */
+                            float* out_probs,             /* [slots * boxes, C] or NULL */
+                            int64_t* out_masks,           /* [slots * boxes]     */
+                            int64_t* bad,                 /* NULL or [1], accumulates */
+                            void* stream);
+
 /* out[j, :] = x[idx[j], :] (zeros where idx[j] < 0): row gather in front of the loss-aware prediction heads (only rows that
  * carry a masked-language / masked-vision target are decoded; "next" row of SURVEY.md section 8f).  Backward =
  * ytvln_scatter_add_rows_f32 with skip_idx = -1. */

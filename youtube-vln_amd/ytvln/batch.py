@@ -6,6 +6,9 @@ sits in HBM.  The loader then only has to ship the un-masked tokens / features /
     randomize_tokens(tokens, mask, mask_action_rate=r) the same with `--mask_action_rate r`  common.py:234-253   (per dataset item)
     randomize_regions(features, probs, mask)         -> (features, targets, targets_mask)  common.py:272-300   (features in place)
     mask_batch(batch, args=args)                     -> the 16-tuple with items 1, 4, 5, 6, 8 replaced
+    expand_options(pool..., index)                   -> items 1, 2, 4, 3 from a pool padded to `boxes` rows per frame
+    expand_ragged(pool..., offsets, index, boxes)    -> the same from the un-padded rows the feature readers return, in one launch
+    RaggedPool(capacity_rows, capacity_frames)       pinned staging + static device buffers around expand_ragged
 
 Draws come from the library's Philox stream (`ops.DropoutState`: seed + device-side counter, so the masks change every call and
 replay inside a hipGraph); passing `p=` / `random_tokens=` (/ `action_choice=`) reproduces the reference functions bit for bit (tests).
@@ -139,7 +142,10 @@ def expand_options(pool_features: Tensor, pool_boxes: Tensor, pool_probs: Tensor
         index         [bs, K, frames] int64: the pool entry shown at each position of each option, -1 = padding frame
 
     and the [bs, K, frames*boxes, ...] tensors of the 16-tuple are gathered in HBM (column 11 of the boxes = the position of the
-    frame inside the option, `all_dataset.py:314`).  Returns (image_features, image_boxes, image_probs, image_masks)."""
+    frame inside the option, `all_dataset.py:314`).  Returns (image_features, image_boxes, image_probs, image_masks).
+
+    Column 11 of a PADDING frame (index -1) is 0 here; `expand_ragged` writes the position there as the reference does
+    (`all_dataset.py:331`).  The difference is confined to rows behind a zero mask."""
     bs, K, frames = index.shape
     P, boxes = pool_masks.shape
     idx = _dev(index, "index").long().reshape(-1)
@@ -152,6 +158,234 @@ def expand_options(pool_features: Tensor, pool_boxes: Tensor, pool_probs: Tensor
     probs = ops.gather_rows(_dev(pool_probs, "pool_probs").reshape(P, -1), idx).view(bs, K, frames * boxes, -1)
     masks = (_dev(pool_masks, "pool_masks").long()[idx.clamp(min=0)] * (idx >= 0).view(n, 1)).view(bs, K, frames * boxes)
     return feats, bx.view(bs, K, frames * boxes, -1), probs, masks
+
+
+def _want(t, name: str, dtype, shape) -> None:
+    """ValueError unless `t` is a contiguous tensor of this dtype and shape (None in `shape` = any size)."""
+    if not torch.is_tensor(t):
+        raise ValueError(f"ytvln.batch: `{name}` must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"ytvln.batch: `{name}` must be {dtype}, got {t.dtype}")
+    if t.dim() != len(shape) or any(w is not None and int(w) != int(g) for w, g in zip(shape, t.shape)):
+        raise ValueError(f"ytvln.batch: `{name}` must have shape {list(shape)}, got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"ytvln.batch: `{name}` must be contiguous")
+
+
+def expand_ragged(pool_features: Tensor, pool_locations: Tensor, pool_probs: Optional[Tensor], offsets: Tensor, index: Tensor, boxes: int,
+                  out: Optional[Sequence[Optional[Tensor]]] = None, bad: Optional[Tensor] = None):
+    """Padding, masks and option expansion from a RAGGED frame pool in one launch (`ytvln_expand_ragged_f32`).  The pool holds what the
+    feature readers return, un-padded: frame p is rows offsets[p] .. offsets[p+1]-1 of
+
+        pool_features [rows, F] fp32   pool_locations [rows, L <= 11] fp32   pool_probs [rows, C] fp32 or None   offsets [frames_in_pool + 1] int64
+        index [bs, K, frames] int64: the pool frame shown at each position of each option, -1 = padding frame
+
+    and every frame is padded (or cut) to `boxes` rows the way `utils/dataset/all_dataset.py:294-345` does on the host: real rows copied,
+    the rest exact zeros with mask 0, box columns L..10 zero.  Returns (image_features [bs, K, frames*boxes, F], image_boxes [.., 12],
+    image_probs [.., C] or None, image_masks [..] int64).  `out=(f, bx, pr, m)` writes into the given contiguous tensors of those shapes
+    (the static inputs of a captured step; `pr` None together with `pool_probs`); whatever they held is overwritten.  `bad` (int64 [1] on
+    the device) accumulates the slots whose index or offsets were out of range; such a slot is all padding.
+
+    Column 11 of the boxes is the position of the frame inside its option for EVERY row, padding frames included, which is what the
+    reference writes (`all_dataset.py:314` and `:331`); `expand_options` writes 0 for padding frames.  The difference is confined to
+    rows behind a zero mask.  Shapes and dtypes are checked first (ValueError, nothing touched); there is no CPU path."""
+    boxes = int(boxes)
+    if boxes <= 0:
+        raise ValueError(f"ytvln.batch: boxes must be positive, got {boxes}")
+    _want(pool_features, "pool_features", torch.float32, (None, None))
+    rows, F = pool_features.shape
+    _want(pool_locations, "pool_locations", torch.float32, (rows, None))
+    L = pool_locations.shape[1]
+    if L > 11:
+        raise ValueError(f"ytvln.batch: `pool_locations` has {L} columns; the boxes hold 11 next to the position column")
+    C = 0
+    if pool_probs is not None:
+        _want(pool_probs, "pool_probs", torch.float32, (rows, None))
+        C = pool_probs.shape[1]
+    _want(offsets, "offsets", torch.int64, (None,))
+    if offsets.numel() < 1:
+        raise ValueError("ytvln.batch: `offsets` holds one entry per pool frame plus one")
+    _want(index, "index", torch.int64, (None, None, None))
+    bs, K, frames = index.shape
+    if frames <= 0:
+        raise ValueError("ytvln.batch: `index` [bs, K, frames] needs frames >= 1")
+    R = frames * boxes
+    if out is not None:
+        if len(out) != 4:
+            raise ValueError("ytvln.batch: `out` is (image_features, image_boxes, image_probs, image_masks)")
+        f, bx, pr, m = out
+        _want(f, "out[0]", torch.float32, (bs, K, R, F))
+        _want(bx, "out[1]", torch.float32, (bs, K, R, 12))
+        if (pr is None) != (pool_probs is None):
+            raise ValueError("ytvln.batch: out[2] (image_probs) and `pool_probs` go together: both given or both None")
+        if pr is not None:
+            _want(pr, "out[2]", torch.float32, (bs, K, R, C))
+        _want(m, "out[3]", torch.int64, (bs, K, R))
+    if bad is not None:
+        _want(bad, "bad", torch.int64, (1,))
+    tensors = [("pool_features", pool_features), ("pool_locations", pool_locations), ("pool_probs", pool_probs), ("offsets", offsets),
+               ("index", index), ("bad", bad)] + ([(f"out[{i}]", t) for i, t in enumerate(out)] if out is not None else [])
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"ytvln.batch: `{name}` must live on the GPU (no CPU path)")
+    dev = pool_features.device
+    if any(t is not None and t.device != dev for _, t in tensors):
+        raise ValueError("ytvln.batch: expand_ragged needs all its tensors on one device")
+    if out is None:
+        f = torch.empty(bs, K, R, F, dtype=torch.float32, device=dev)
+        bx = torch.empty(bs, K, R, 12, dtype=torch.float32, device=dev)
+        pr = torch.empty(bs, K, R, C, dtype=torch.float32, device=dev) if pool_probs is not None else None
+        m = torch.empty(bs, K, R, dtype=torch.int64, device=dev)
+    call("ytvln_expand_ragged_f32", ops._ptr(pool_features), ops._ptr(pool_locations), ops._ptr(pool_probs), ops._ptr(offsets),
+         offsets.numel() - 1, rows, ops._ptr(index), bs * K * frames, frames, boxes, F, L, C, ops._ptr(f), ops._ptr(bx), ops._ptr(pr),
+         ops._ptr(m), ops._ptr(bad), ops._stream())
+    return f, bx, pr, m
+
+
+class RaggedPool:
+    """The frames of one step as the feature readers return them, shipped once: pinned host staging buffers and static device buffers of
+    fixed capacity, allocated here and reused every step.
+
+        pool = RaggedPool(capacity_rows, capacity_frames)
+        ids  = [pool.add(key, *reader[key], max_rows=boxes) for key in ...]      # one frame each; a key seen before costs nothing
+        idx  = pool.index(options, frames)                                         # nested lists of ids -> int64 [bs, K, frames]
+        pool.upload()                                                              # the used rows only, non-blocking, current stream
+        f, bx, pr, m = pool.expand(idx, boxes, out=static_inputs)                  # one launch (expand_ragged)
+        pool.reset()                                                               # next step
+
+    `add` converts fp64 arrays (the readers' locations and probabilities) to fp32 exactly as the reference's `.float()` does.  The device
+    buffers never move, so a captured `expand` replays on whatever the last `upload()` brought.  `reset()` waits for the last upload's
+    copies before the staging buffers are written again.  Without a GPU the object still does its host bookkeeping (tests); `upload` and
+    `expand` then raise."""
+
+    def __init__(self, capacity_rows: int, capacity_frames: int, feature_dim: int = 2048, loc_dim: int = 11, num_classes: int = 1601,
+                 device=None, probs: bool = True):
+        capacity_rows, capacity_frames = int(capacity_rows), int(capacity_frames)
+        if capacity_rows < 1 or capacity_frames < 1:
+            raise ValueError(f"ytvln.batch: RaggedPool capacities must be positive, got {capacity_rows} rows, {capacity_frames} frames")
+        if not 0 <= int(loc_dim) <= 11:
+            raise ValueError(f"ytvln.batch: loc_dim must be within [0, 11], got {loc_dim}")
+        self.capacity_rows, self.capacity_frames = capacity_rows, capacity_frames
+        self.feature_dim, self.loc_dim, self.num_classes = int(feature_dim), int(loc_dim), int(num_classes)
+        if device is None and torch.cuda.is_available():
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device) if device is not None else None
+        if self.device is not None and self.device.type != "cuda":
+            raise RuntimeError(f"ytvln.batch: RaggedPool's device buffers must live on the GPU (no CPU path), got {self.device}")
+        pin = self.device is not None
+
+        def host(*shape, dtype=torch.float32):
+            return torch.zeros(*shape, dtype=dtype, pin_memory=pin)
+
+        self.host_features = host(capacity_rows, self.feature_dim)
+        self.host_locations = host(capacity_rows, self.loc_dim)
+        self.host_probs = host(capacity_rows, self.num_classes) if probs else None
+        self.host_offsets = host(capacity_frames + 1, dtype=torch.int64)
+        self.features = self.locations = self.probs = self.offsets = self.bad = None
+        if self.device is not None:
+            self.features = torch.zeros(capacity_rows, self.feature_dim, device=self.device)
+            self.locations = torch.zeros(capacity_rows, self.loc_dim, device=self.device)
+            self.probs = torch.zeros(capacity_rows, self.num_classes, device=self.device) if probs else None
+            self.offsets = torch.zeros(capacity_frames + 1, dtype=torch.int64, device=self.device)
+            self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)        # slots with an out-of-range index, summed over the calls
+        self.rows = self.frames = 0
+        self.bytes_uploaded = 0
+        self._ids = {}
+        self._uploaded = None
+
+    @staticmethod
+    def _rows_of(x, name: str, cols: int, n: int) -> Tensor:
+        t = x if torch.is_tensor(x) else torch.from_numpy(x)
+        if t.dim() != 2 or t.shape[1] < cols or t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"ytvln.batch: `{name}` must be an fp32 or fp64 array [n, {cols}], got {t.dtype} {list(t.shape)}")
+        return t[:n, :cols]
+
+    def add(self, key, features, locations, probs=None, max_rows: Optional[int] = None) -> int:
+        """Append one frame (the tuple a reader's `__getitem__` returns) and return its pool id.  A key seen since the last `reset()`
+        returns its id and copies nothing.  `max_rows` keeps the first rows only (`num_boxes = min(len, max_num_boxes)`)."""
+        known = self._ids.get(key)
+        if known is not None:
+            return known
+        n = int(features.shape[0])
+        if max_rows is not None:
+            n = min(n, int(max_rows))
+        if (probs is None) != (self.host_probs is None):
+            raise ValueError("ytvln.batch: this RaggedPool was built with probs=%s" % (self.host_probs is not None))
+        f = self._rows_of(features, "features", self.feature_dim, n)
+        loc = self._rows_of(locations, "locations", self.loc_dim, n)
+        pr = self._rows_of(probs, "probs", self.num_classes, n) if probs is not None else None
+        if f.shape[1] != self.feature_dim or (pr is not None and pr.shape[1] != self.num_classes):
+            raise ValueError("ytvln.batch: feature / class width does not match the pool")
+        if loc.shape[0] != n or f.shape[0] != n or (pr is not None and pr.shape[0] != n):
+            raise ValueError(f"ytvln.batch: features, locations and probs of a frame need the same number of rows (>= {n} here)")
+        if self.frames + 1 > self.capacity_frames:
+            raise ValueError(f"ytvln.batch: RaggedPool is full: capacity_frames = {self.capacity_frames}")
+        if self.rows + n > self.capacity_rows:
+            raise ValueError(f"ytvln.batch: {self.rows} + {n} rows exceed RaggedPool's capacity_rows = {self.capacity_rows}")
+        a, b = self.rows, self.rows + n
+        self.host_features[a:b].copy_(f)            # fp64 -> fp32 by copy_: the rounding of `.float()`
+        self.host_locations[a:b].copy_(loc)
+        if pr is not None:
+            self.host_probs[a:b].copy_(pr)
+        pid = self.frames
+        self.frames, self.rows = pid + 1, b
+        self.host_offsets[pid + 1] = b
+        self._ids[key] = pid
+        return pid
+
+    @staticmethod
+    def index(options, frames: int) -> Tensor:
+        """int64 [bs, K, frames] from nested lists of pool ids (`options[item][option]` = the ids of that option's frames in order):
+        cut to `frames` positions, padded with -1."""
+        bs = len(options)
+        K = max((len(o) for o in options), default=0)
+        if any(len(o) != K for o in options):
+            raise ValueError("ytvln.batch: every item needs the same number of options")
+        idx = torch.full((bs, K, int(frames)), -1, dtype=torch.int64)
+        for i, item in enumerate(options):
+            for k, ids in enumerate(item):
+                ids = list(ids)[:int(frames)]
+                if ids:
+                    idx[i, k, :len(ids)] = torch.as_tensor(ids, dtype=torch.int64)
+        return idx
+
+    def _need_device(self, what: str) -> None:
+        if self.device is None:
+            raise RuntimeError(f"ytvln.batch: RaggedPool.{what} needs the GPU (no CPU path)")
+
+    def upload(self) -> None:
+        """Non-blocking copies of the used prefix of each buffer, and of `offsets`, to the device on the current stream.  Entries of
+        `offsets` beyond the used frames repeat the last value: a stale index entry is an empty frame, not a wild read."""
+        self._need_device("upload")
+        self.host_offsets[self.frames + 1:] = self.rows
+        moved = 0
+        pairs = [(self.features, self.host_features), (self.locations, self.host_locations)]
+        if self.host_probs is not None:
+            pairs.append((self.probs, self.host_probs))
+        for d, h in pairs:
+            if self.rows:
+                d[:self.rows].copy_(h[:self.rows], non_blocking=True)
+            moved += self.rows * h.shape[1] * h.element_size()
+        self.offsets.copy_(self.host_offsets, non_blocking=True)
+        moved += self.host_offsets.numel() * self.host_offsets.element_size()
+        self.bytes_uploaded = moved
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+
+    def expand(self, index: Tensor, boxes: int, out=None):
+        """`expand_ragged` on the device buffers (a CPU `index` is uploaded first)."""
+        self._need_device("expand")
+        if torch.is_tensor(index) and not index.is_cuda:
+            index = index.to(self.device, non_blocking=True)
+        return expand_ragged(self.features, self.locations, self.probs, self.offsets, index, boxes, out=out, bad=self.bad)
+
+    def reset(self) -> None:
+        """Start the next step: forget the frames and keys (the buffers stay)."""
+        if self._uploaded is not None:
+            self._uploaded.synchronize()           # the staging buffers are about to be overwritten
+            self._uploaded = None
+        self.rows = self.frames = 0
+        self._ids = {}
 
 
 def mask_batch(batch: Sequence[Tensor], vocab_size: int = VOCAB_SIZE, mask_token_id: int = MASK_TOKEN_ID, masked_language: bool = True,

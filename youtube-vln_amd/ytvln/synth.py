@@ -183,6 +183,54 @@ def make_pool(bs: int, K: int, T: int, frames: int, boxes: int, F: int = 2048, C
     return pf, pb, pp.astype(np.float32), pm, index, tokens, (tokens > 0).astype(np.int64)
 
 
+def make_ragged_pool(bs: int, K: int, T: int, frames: int, boxes: int, F: int = 2048, C: int = 1601, vocab: int = 30522, seed: int = 1234):
+    """The batch of make_pool in the RAGGED form consumed by ytvln.batch.RaggedPool / expand_ragged: every distinct frame as a feature
+    reader returns it -- (features [n, F] fp32, locations [n, 11] fp64, probs [n, C] fp64) with its own n, drawn from 1 .. boxes + 3, so
+    some frames exceed `boxes` and get cut -- plus, instead of an index tensor, nested lists `options[item][option]` = the pool ids of
+    that option's frames in order (RaggedPool.index pads them).  Option structure as in make_pool: 0 positive, 1-2 caption negatives
+    sharing its frames, 3-4 frame permutations, 5-6 some frames swapped for other photos.  Returns (frames_list, options,
+    tokens [bs,K,T], instr_mask [bs,K,T])."""
+    rs = np.random.RandomState(seed)
+    per_item = frames + 2 * (frames // 2)
+    P = bs * per_item
+    pool = []
+    for n in rs.randint(1, boxes + 4, size=P):
+        f = np.maximum(rs.standard_normal((n, F)).astype(np.float32), 0.0)
+        f[0] = f.mean(0)                                       # row 0 of each frame: mean feature, whole-image box (features_reader.py:170-177)
+        loc = rs.uniform(0, 1, (n, 11))
+        loc[0, :5] = [0, 0, 1, 1, 1]
+        logits = rs.standard_normal((n, C)) * 3.0
+        logits -= logits.max(-1, keepdims=True)
+        pr = np.exp(logits)
+        pool.append((f, loc, pr / pr.sum(-1, keepdims=True)))
+    options = []
+    tokens = np.zeros((bs, K, T), np.int64)
+    for i in range(bs):
+        base = i * per_item
+        L = rs.randint(min(4, frames), frames + 1)
+        path = base + np.arange(L)
+        spare = base + frames + np.arange(2 * (frames // 2))
+        ins = []
+        for _ in range(3):
+            n = rs.randint(min(20, T - 2), T - 1)
+            t = np.zeros(T, np.int64)
+            t[0], t[1:1 + n], t[1 + n] = 101, rs.randint(1000, vocab, size=n), 102
+            ins.append(t)
+        item = []
+        for k in range(K):
+            row = path.copy()
+            if k in (3, 4):
+                row = path[rs.permutation(L)]
+            elif k >= 5:
+                sw = np.nonzero(rs.rand(L) < 0.5)[0]
+                sw = sw[sw > 0][:frames // 2]
+                row[sw] = spare[(k - 5) * (frames // 2):(k - 5) * (frames // 2) + len(sw)]
+            item.append([int(x) for x in row])
+            tokens[i, k] = ins[k] if k in (1, 2) else ins[0]
+        options.append(item)
+    return pool, options, tokens, (tokens > 0).astype(np.int64)
+
+
 def to_torch(batch: List[np.ndarray], device="cpu"):
     import torch
     return [torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in batch]
