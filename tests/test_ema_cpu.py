@@ -149,7 +149,7 @@ def _stubbed(monkeypatch, **attrs):
     _build_launch produce); every ops.call is recorded instead of run.  -> (optimizer, the recorded calls)."""
     import struct
     from ytvln import ops
-    from ytvln.optimization import AdamW, lamb_tables
+    from ytvln.optimization import AdamW, lamb_tables, new_arena
     seen = []
     monkeypatch.setattr(ops, "call", lambda name, *a: seen.append((name, a)))
     monkeypatch.setattr(ops, "_stream", lambda: 0)
@@ -164,8 +164,7 @@ def _stubbed(monkeypatch, **attrs):
     index = {id(ps[0]): (0, 5), id(ps[1]): (8, 8)}
     flat = {k: torch.zeros(16) for k in "pgmv"}
     flat["p"][0:5], flat["p"][8:16] = 1.0, 2.0
-    opt._arena = dict(flat, index=index, ids=[id(p) for p in ps], pb=None, pb_versions={}, gb=None, partials=None, clip=None, lamb=None,
-                      ema=None)
+    opt._arena = new_arena(flat, index, [id(p) for p in ps])
     opt._written = set()
     opt._launch = []
     for gi, p in enumerate(ps):
@@ -252,16 +251,17 @@ def test_swap_runs_over_every_launch_class_and_blocks_training_until_swapped_bac
 
 
 def test_prepare_replay_refuses_on_off_changed_after_a_capture_but_not_a_changed_decay():
+    from ytvln.optimization import CaptureSettings
     opt = _opt()
     opt._launch = []                      # (no launch classes: prepare_replay uploads nothing)
     opt.ema_decay = 0.9
     opt.prepare_replay()                  # nothing captured yet: any setting goes
-    opt._captured_ema = False             # as a capture with the feature off leaves it
+    opt._captured = CaptureSettings(ema=False)           # as a capture with the feature off leaves it
     with pytest.raises(RuntimeError, match="capture the step again"):
         opt.prepare_replay()
     opt.ema_decay = None
     opt.prepare_replay()
-    opt._captured_ema = True              # as a capture with it on leaves it
+    opt._captured = CaptureSettings(ema=True)           # as a capture with it on leaves it
     with pytest.raises(RuntimeError, match="capture the step again"):
         opt.prepare_replay()
     n = opt.ema_updates

@@ -146,16 +146,16 @@ def test_adamw_allocates_no_clip_buffers_by_default():
 
 def test_prepare_replay_refuses_settings_changed_after_a_capture():
     """A captured step bakes the settings in: the host-side check needs no device."""
-    from ytvln.optimization import AdamW
+    from ytvln.optimization import AdamW, CaptureSettings
     opt = AdamW([nn.Parameter(torch.zeros(4))], lr=1e-3)
     opt._launch = []                      # (no launch classes: prepare_replay uploads nothing)
     opt.prepare_replay()                  # nothing captured yet: any setting goes
-    opt._captured_clip = None             # as a capture with the feature off leaves it
+    opt._captured = CaptureSettings(clip=None)      # as a capture with the feature off leaves it
     opt.prepare_replay()
     opt.max_grad_norm = 1.0
     with pytest.raises(RuntimeError, match="capture the step again"):
         opt.prepare_replay()
-    opt._captured_clip = (1.0, False)     # as a capture with max_grad_norm = 1 leaves it
+    opt._captured = CaptureSettings(clip=(1.0, False))     # as a capture with max_grad_norm = 1 leaves it
     opt.prepare_replay()
     opt.max_grad_norm = 2.0
     with pytest.raises(RuntimeError, match="capture the step again"):

@@ -168,17 +168,17 @@ def test_anything_but_a_bool_raises_when_the_step_is_taken(bad):
 
 def test_prepare_replay_refuses_a_setting_changed_after_a_capture():
     """A captured step bakes the setting in: the host-side check needs no device."""
-    from ytvln.optimization import AdamW
+    from ytvln.optimization import AdamW, CaptureSettings
     opt = AdamW([nn.Parameter(torch.zeros(4))], lr=1e-3)
     opt._launch = []                      # (no launch classes: prepare_replay uploads nothing)
     opt.trust_ratio = True
     opt.prepare_replay()                  # nothing captured yet: any setting goes
-    opt._captured_lamb = False            # as a capture with the feature off leaves it
+    opt._captured = CaptureSettings(lamb=False)          # as a capture with the feature off leaves it
     with pytest.raises(RuntimeError, match="capture the step again"):
         opt.prepare_replay()
     opt.trust_ratio = False
     opt.prepare_replay()
-    opt._captured_lamb = True             # as a capture with it on leaves it
+    opt._captured = CaptureSettings(lamb=True)          # as a capture with it on leaves it
     with pytest.raises(RuntimeError, match="capture the step again"):
         opt.prepare_replay()
     opt.trust_ratio = True

@@ -113,7 +113,7 @@ def main():
         res["delta_ms_on_minus_off"] = res["step_ms"]["on"]["min"] - res["step_ms"]["off"]["min"]
         opt = runs["on"]["opt"]
         partials, clip = opt.clip_buffers()
-        g = opt.flat_grads()
+        g = opt.flat_grad()
         elems = sum(numel for _, numel in opt._arena["index"].values())
 
         def sumsq():

@@ -69,7 +69,7 @@ def main():
         opt.launch_classes()
     t = protocol(dev, {"adamw": plain, "lamb": lamb}, a.reps, a.passes)
     partials, trust, report = opt.lamb_buffers()
-    g = opt.flat_grads()
+    g = opt.flat_grad()
 
     def parts(c):
         return partials[2 * c["rec0"]:2 * (c["rec0"] + c["n"])]

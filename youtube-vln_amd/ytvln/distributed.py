@@ -23,7 +23,6 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-import struct
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -32,7 +31,7 @@ from torch import nn
 
 from . import _lib
 from . import ops as _ops
-from .optimization import CHUNK
+from .optimization import chunk_table
 
 
 def get_rank(default: int = 0) -> int:
@@ -279,8 +278,8 @@ class GradBucketReducer:
             for p in b["params"]:
                 self._of[id(p)] = b
             if send is not None:        # pack table of the bucket: CHUNK-element records, as the AdamW tables (one workgroup each)
-                rec = b"".join(struct.pack("<qqff", o, min(CHUNK, b["hi"] - o), 0.0, 0.0) for o in range(b["lo"], b["hi"], CHUNK))
-                b["pack"] = (torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(flat.device), len(rec) // 24)
+                rec, n = chunk_table([(b["lo"], b["hi"] - b["lo"], 0.0)])
+                b["pack"] = (torch.frombuffer(rec, dtype=torch.uint8).to(flat.device), n)
         self._hooks = []
         self._late: Optional[str] = None
         self.reset()
@@ -597,18 +596,9 @@ class GraphedTrainStep:
         optimizer.zero_grad()
         optimizer.grad_scale = 1.0 / self.world
         optimizer.exchange_dtype = self.grad_dtype
-        if _ops.get_matmul_precision() == "bf16" and hasattr(optimizer, "bf16_arena"):
+        if _ops.get_matmul_precision() == "bf16":
             optimizer.bf16_arena()          # the one-time cast of the whole weight arena happens here, eagerly: not recorded into a graph
-        if self.bf16:
-            optimizer.grad_bf16()           # the exchange buffer is allocated eagerly, outside the graphs' pools
-        if hasattr(optimizer, "clip_settings") and optimizer.clip_settings() is not None:
-            optimizer.clip_buffers()        # gradient clipping on: its partials and its record, eagerly as well
-        if hasattr(optimizer, "lamb_setting") and optimizer.lamb_setting():
-            optimizer.lamb_buffers()        # LAMB trust ratio on: its partials, ratios and report rows
-        if hasattr(optimizer, "ema_setting") and optimizer.ema_setting() is not None:
-            optimizer.ema_buffers()         # EMA of the weights on: its shadow arena
-        if hasattr(optimizer, "stats_setting") and optimizer.stats_setting():
-            optimizer.stats_buffers()       # per-tensor statistics on: their partials and report rows
+        optimizer.capture_buffers()         # the exchange buffer and the buffers of the optimizer's opt-in features: eagerly, outside the graphs' pools
         torch.cuda.synchronize()
         flat = optimizer.flat_grad()
         # the buffer the collectives work on: the fp32 arena, or its bf16 copy (same offsets; slices stay element ranges)
@@ -815,11 +805,6 @@ class GraphedTrainStep:
             self.opt.prepare_replay()                   # hyper-parameters of this step: uploaded before the first per-group update
             tables = self.opt.group_tables(self._group_slices, owner=self)
             overlap = self.comm is not None or not self.exchange          # (torch.distributed data plane: everything in stream order)
-            # gradient clipping: per group only the sum of squares; the coefficient and every update wait for the last group's partials
-            clip = hasattr(self.opt, "clip_settings") and self.opt.clip_settings() is not None
-            # LAMB trust ratio: the three launches run over whole launch classes, so every update waits for the last group as well
-            lamb = hasattr(self.opt, "lamb_setting") and self.opt.lamb_setting()
-            slot = 0
             for k, g in enumerate(self.graphs):
                 g.replay()
                 if not self._group_slices[k]:
@@ -829,10 +814,7 @@ class GraphedTrainStep:
                         self.opt.pack_grads(tables[k])
                     for lo, hi in self._group_slices[k]:
                         dist.all_reduce(xbuf[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
-                    if clip:
-                        slot = self.opt.sumsq_tables(tables[k], slot)
-                    elif not lamb:
-                        self.opt.launch_tables(tables[k])
+                    self.opt.group_update(tables[k])
                     continue
                 self._events[k].record(cur)
                 self._comm_stream.wait_event(self._events[k])
@@ -847,26 +829,13 @@ class GraphedTrainStep:
                     e1.record(self._comm_stream)
                     self._prof_events = (e0, e1)
                 with torch.cuda.stream(self._comm_stream):
-                    if clip:
-                        slot = self.opt.sumsq_tables(tables[k], slot)
-                    elif not lamb:
-                        self.opt.launch_tables(tables[k])
-            if clip or lamb:
-                with torch.cuda.stream(self._comm_stream) if overlap else contextlib.nullcontext():
-                    if clip:
-                        self.opt.clip_coef(slot)
-                    if lamb:
-                        self.opt.launch_classes()
-                    else:
-                        for t in tables:
-                            self.opt.launch_tables(t)
-            if hasattr(self.opt, "stats_setting") and self.opt.stats_setting():
-                # per-tensor statistics: once, behind the last update of the step on the stream the updates ran on
-                with torch.cuda.stream(self._comm_stream) if overlap else contextlib.nullcontext():
-                    self.opt.tensor_stats_launch()
+                    self.opt.group_update(tables[k])
+            # whatever the optimizer's opt-in features deferred to the end of the step (a global gradient norm, norms over whole tensors,
+            # the per-tensor report): on the stream the group updates ran on, before the compute stream waits for it
+            with torch.cuda.stream(self._comm_stream) if overlap else contextlib.nullcontext():
+                self.opt.finish_group_step(tables)
             if overlap:
                 cur.wait_stream(self._comm_stream)
-            self.opt.finish_group_step()
             if scheduler is not None:
                 scheduler.step()
             return self.loss

@@ -8,10 +8,9 @@ received a gradient are moved into one flat fp32 arena (their `.data` / `.grad` 
 arenas, and a whole step is one HIP kernel launch per (param-group, step-count) class instead of ~8 ATen kernels per
 tensor x 541 tensors.  The flat gradient arena is also what the data-parallel all-reduce buckets (ytvln/distributed.py).
 
-Beyond the reference (it has no gradient clipping): two plain attributes, `optimizer.max_grad_norm` and `optimizer.skip_nonfinite`, bound
-the global gradient norm inside the step, `optimizer.trust_ratio` switches the update to LAMB's layer-wise trust ratio,
-`optimizer.ema_decay` keeps an exponential moving average of the weights in a shadow arena, and `optimizer.tensor_stats` reports norms,
-maxima and non-finite counts per parameter tensor -- see the `AdamW` docstring.
+Beyond the reference, as plain attributes (the `AdamW` docstring): `max_grad_norm` / `skip_nonfinite` bound the global gradient norm inside
+the step, `trust_ratio` switches the update to LAMB's layer-wise trust ratio, `ema_decay` keeps an exponential moving average of the weights
+in a shadow arena, `tensor_stats` reports norms, maxima and non-finite counts per parameter tensor.
 """
 from __future__ import annotations
 
@@ -20,7 +19,7 @@ import math
 import numbers
 import struct
 from collections import OrderedDict
-from typing import Dict, List
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 from torch.optim import Optimizer
@@ -44,6 +43,35 @@ def lamb_tables(tensors, chunk=CHUNK):
         rec += [int(k)] * ((numel + chunk - 1) // chunk)
         first.append(len(rec))
     return first, rec
+
+
+def chunk_table(runs, chunk=CHUNK):
+    """(bytearray, number of records): the chunk table of `runs` = [(arena offset, numel, weight decay)], every run cut into records
+    (offset, length, weight decay, 0) of at most `chunk` elements."""
+    rec, n = bytearray(), 0
+    for o, numel, wd in runs:
+        for c in range(0, numel, chunk):
+            rec += struct.pack("<qqff", o + c, min(chunk, numel - c), wd, 0.0)
+            n += 1
+    return rec, n
+
+
+def new_arena(flat, index, ids):
+    """The arena record: the flat fp32 tensors p, g, m, v of `flat`, index = {id(param): (offset, numel)}, ids = the members in order, and
+    every lazily created buffer still absent: the bf16 weight copy (pb, pb_versions), the bf16 exchange buffer (gb) and the buffers of the
+    opt-in features (partials and clip; lamb; ema; stats)."""
+    return dict(flat, index=index, ids=ids, pb=None, pb_versions={}, gb=None, partials=None, clip=None, lamb=None, ema=None, stats=None)
+
+
+class CaptureSettings(NamedTuple):
+    """What a captured step bakes in (AdamW.capture_settings()): each field changes which launches a step records."""
+    clip: Optional[tuple] = None        # None or (max_norm, skip_nonfinite)
+    lamb: bool = False
+    ema: bool = False                   # on / off only: decay and warm-up travel by value
+    stats: bool = False
+
+
+_SETTING_ATTRS = {"clip": "max_grad_norm / skip_nonfinite", "lamb": "trust_ratio", "ema": "ema_decay (on / off)", "stats": "tensor_stats"}
 
 
 class ConstantLRSchedule(LambdaLR):
@@ -112,72 +140,65 @@ class WarmupCosineWithHardRestartsSchedule(LambdaLR):
 
 
 class AdamW(Optimizer):
-    """The reference's AdamW, fused (module docstring), plus opt-in global gradient-norm clipping.
+    """The reference's AdamW, fused (module docstring), plus four opt-in features the reference does not have.
 
-    max_grad_norm (attribute, default None): a number > 0 bounds the global L2 norm of the gradient the update applies -- after the
-        data-parallel exchange and its 1/world average, over the bf16 sums when the exchange is bf16 -- with
-        torch.nn.utils.clip_grad_norm_'s formula, coef = min(1, max_norm / (norm + 1e-6)); float("inf") measures the norm without clipping.
-    skip_nonfinite (attribute, default False): a step whose gradient norm is inf or NaN leaves parameters, moments and the bf16 weight copy
-        untouched and is counted.  Without it a non-finite norm behaves as in torch (error_if_nonfinite=False): the coefficient becomes 0 or
-        NaN and goes into the update.
-    Both are plain attributes: not constructor arguments, not in `param_groups` / `defaults`, not in `state_dict()` (checkpoints stay
-    interchangeable with the reference).  With both at their defaults a step launches exactly the kernels it always launched.  With either
-    set, every step -- eager, while capturing, on replay -- runs, between the gradient exchange and the update: ytvln_grad_sumsq over
-    every launch class, one ytvln_grad_clip_coef, then ytvln_adamw_clip per class; no host synchronisation, no atomics, fixed summation
-    orders.  Invalid values (<= 0, NaN, not a number) raise ValueError when the step is taken.
+    What holds for every opt-in attribute below: it is a plain attribute -- not a constructor argument, not in `param_groups` / `defaults`,
+    not in `state_dict()` (checkpoints stay interchangeable with the reference) -- and is validated when the step is taken: an invalid value
+    raises a ValueError that names it, before anything is exchanged, launched or recorded.  Off (the default), a step launches and allocates
+    exactly what it always did.  On, every step -- eager, while capturing, on replay -- runs the feature's launches: no host
+    synchronisation, no atomics, fixed summation orders.  A captured step bakes the settings in (`capture_settings()`): changing one
+    afterwards makes the next `prepare_replay()` raise; capture the step again.  Capturing with a feature on needs its device buffers, which
+    must not live in a graph's pool: the first eager step with it on allocates them, or `capture_buffers()`, or the feature's own accessor.
+    They are dropped with the arena (load_state_dict, a changed parameter set) -- the counts kept in them restart -- and are never part of
+    `state_dict()`.
 
-    The decision to skip is taken on the device: the host cannot know it without a sync, so on a skipped step `state[p]["step"]` (the
-    bias-correction count) and an LR scheduler still advance.  `grad_norm()` is a 0-d device view of the last step's norm (no sync);
-    `skipped_steps()` reads the count of skipped steps back (synchronises); the count restarts when the arenas are rebuilt
-    (load_state_dict, a changed parameter set).
+    max_grad_norm (default None): a number > 0 bounds the global L2 norm of the gradient the update applies -- after the data-parallel
+        exchange and its 1/world average, over the bf16 sums when the exchange is bf16 -- with torch.nn.utils.clip_grad_norm_'s formula,
+        coef = min(1, max_norm / (norm + 1e-6)); float("inf") measures the norm without clipping.  Anything else (<= 0, NaN, not a
+        number) is invalid.
+    skip_nonfinite (default False): a step whose gradient norm is inf or NaN leaves parameters, moments and the bf16 weight copy untouched
+        and is counted.  Without it a non-finite norm behaves as in torch (error_if_nonfinite=False): the coefficient becomes 0 or NaN and
+        goes into the update.
+    With either set, a step runs, between the gradient exchange and the update: ytvln_grad_sumsq over every launch class, one
+    ytvln_grad_clip_coef, then ytvln_adamw_clip per class.  The decision to skip is taken on the device: the host cannot know it without a
+    sync, so on a skipped step `state[p]["step"]` (the bias-correction count) and an LR scheduler still advance.  `grad_norm()` is a 0-d
+    device view of the last step's norm (no sync); `skipped_steps()` reads the count of skipped steps back (synchronises).  Both settings
+    are baked into a capture; the two small buffers are `clip_buffers()`.
 
-    A captured step bakes both settings into the graph: changing either afterwards makes the next `prepare_replay()` raise; capture the
-    step again.  Capturing with the feature on needs its two small device buffers, which the first eager step with the feature on (or
-    `clip_buffers()`) allocates.
+    trust_ratio (default False; anything but a bool is invalid): True turns the update into LAMB (You et al., 2020) -- the AdamW direction
+        with the decay inside it, r = b * m / (sqrt(v) + eps) + wd * p (b: the bias correction), rescaled per parameter tensor:
+        p -= lr * trust * r with trust = ||p|| / ||r|| over the whole tensor.  Tensors of a group without weight decay (bias, LayerNorm:
+        the BERT LAMB recipe) and tensors with a zero or non-finite norm keep trust = 1.  The gradient is the one plain AdamW would read
+        (after the exchange, times grad_scale, times the clip coefficient with clipping on: LAMB's usual pre-normalisation IS
+        max_grad_norm = 1).  Per launch class three launches replace the one update: ytvln_lamb_stage1 (moments and per-record partial
+        norms), ytvln_lamb_trust, ytvln_lamb_stage2 (the update, and the bf16 weight copy): 40 bytes per parameter against 28.  With False
+        the decay stays after the update.  Buffers: `lamb_buffers()`.  `trust_ratios()` is a device view [tensors in arena order, 4] of the
+        last step's rows [||p||, ||r||, trust, 0].
 
-    trust_ratio (attribute, default False): True turns the update into LAMB (You et al., 2020) -- the AdamW direction with the decay inside
-        it, r = b * m / (sqrt(v) + eps) + wd * p (b: the bias correction), rescaled per parameter tensor: p -= lr * trust * r with
-        trust = ||p|| / ||r|| over the whole tensor.  Tensors of a group without weight decay (bias, LayerNorm: the BERT LAMB recipe) and
-        tensors with a zero or non-finite norm keep trust = 1.  The gradient is the one plain AdamW would read (after the exchange, times
-        grad_scale, times the clip coefficient with clipping on: LAMB's usual pre-normalisation IS max_grad_norm = 1).  Per launch class
-        three launches replace the one update: ytvln_lamb_stage1 (moments and per-record partial norms), ytvln_lamb_trust, ytvln_lamb_stage2
-        (the update, and the bf16 weight copy): 40 bytes per parameter against 28; no host synchronisation, no atomics, fixed summation
-        orders.  A plain attribute like the two above (anything but a bool raises ValueError when the step is taken), not in state_dict();
-        with False the decay stays after the update and a step launches exactly what it always launched.  Baked into a captured step like
-        the clip settings; its small buffers come from the first eager step with it on or from `lamb_buffers()`.  `trust_ratios()` is a
-        device view [tensors in arena order, 4] of the last step's rows [||p||, ||r||, trust, 0].
+    ema_decay (default None; a bool, a NaN or a value outside (0, 1) is invalid): a number strictly inside (0, 1) keeps an exponential
+        moving average of the weights (timm's ModelEmaV2) in a shadow arena with the offsets of the parameter arena: the shadow starts as a
+        copy of the weights, and behind the update launches of every chunk table one ytvln_ema_update applies e = fma(w, p - e, e) in fp32
+        to the parameters the update just wrote (12 bytes per parameter, a launch of its own).  w = float32(1 - decay_eff) is computed on
+        the host in double and travels through slot 6 of the per-class hyper record, so `ema_decay` and `ema_warmup` may change between
+        replays of a captured step: only on / off is baked into a capture.
+    ema_warmup (default False; anything but a bool is invalid): True gives decay_eff = min(ema_decay, (1 + n) / (10 + n)), n = `ema_updates`.
+    ema_updates: the host count n of EMA updates taken.  Like `state[p]["step"]` it advances on a step the device decides to skip
+        (skip_nonfinite): the host cannot know the decision without a sync; the shadow itself is left untouched by such a step.
+    The shadow (`ema_buffers()`) is the one buffer that survives an arena rebuild: members that had a shadow keep it, new members start from
+    their current value; parameters that never receive a gradient have none -- their EMA is the parameter itself.  Every data-parallel rank
+    computes the same shadow: nothing is exchanged.  `ema_parameters()` maps parameters to their shadow views, `ema_state_dict(model)` is the
+    model file with the shadow weights, `swap_ema()` / `with optimizer.ema_weights():` exchange weights and shadow in place for evaluation
+    (views, arena slots and captured graphs stay valid; stepping while swapped raises RuntimeError), `ema_checkpoint(model)` /
+    `load_ema(state, model)` carry the shadow through checkpoints (ytvln.utils_init.save_model, ytvln.vilbert_init.restore_checkpoint).
 
-    ema_decay (attribute, default None): a number strictly inside (0, 1) keeps an exponential moving average of the weights (timm's
-        ModelEmaV2) in a shadow arena with the offsets of the parameter arena: the shadow starts as a copy of the weights, and behind the
-        update launches of every chunk table one ytvln_ema_update applies e = fma(w, p - e, e) in fp32 to the parameters the update just
-        wrote (12 bytes per parameter, a launch of its own; no host synchronisation, no atomics).  w = float32(1 - decay_eff) is computed
-        on the host in double and travels through slot 6 of the per-class hyper record, so `ema_decay` and `ema_warmup` may change
-        between replays of a captured step; only on / off is baked into a capture (`prepare_replay()` raises when it differs).
-    ema_warmup (attribute, default False): True gives decay_eff = min(ema_decay, (1 + n) / (10 + n)), n = `ema_updates`.
-    ema_updates (attribute): the host count n of EMA updates taken.  Like `state[p]["step"]` it advances on a step the device decides
-        to skip (skip_nonfinite): the host cannot know the decision without a sync; the shadow itself is left untouched by such a step.
-    All three are plain attributes: not constructor arguments, not in `param_groups` / `defaults` / `state_dict()`.  A bool, a NaN or a
-    value outside (0, 1) for ema_decay, or anything but a bool for ema_warmup, raises ValueError when the step is taken.  With ema_decay =
-    None a step launches exactly what it always launched and nothing is allocated.  The shadow (`ema_buffers()`, created by the first eager
-    step with the feature on) survives an arena rebuild: members that had a shadow keep it, new members start from their current value;
-    parameters that never receive a gradient have none -- their EMA is the parameter itself.  Every data-parallel rank computes the same
-    shadow: nothing is exchanged.  `ema_parameters()` maps parameters to their shadow views, `ema_state_dict(model)` is the model file with
-    the shadow weights, `swap_ema()` / `with optimizer.ema_weights():` exchange weights and shadow in place for evaluation (views, arena
-    slots and captured graphs stay valid; stepping while swapped raises RuntimeError), `ema_checkpoint(model)` / `load_ema(state, model)`
-    carry the shadow through checkpoints (ytvln.utils_init.save_model, ytvln.vilbert_init.restore_checkpoint).
-
-    tensor_stats (attribute, default False): True makes every step -- eager, while capturing, on replay -- report per parameter tensor what
-        the step did: behind the update launches (and the EMA launch) of the step, ytvln_tensor_stats_stage1 and ytvln_tensor_stats_stage2
-        run over every launch class's whole chunk table (8 bytes per parameter read, 6 with bf16 gradients; no host synchronisation, no
-        atomics, fixed summation orders).  `tensor_stats_report()` returns two device views in arena order: rows [||g||, max |g|, ||p||,
-        max |p|] over the finite elements and rows [non-finite elements of g, of p, steps so far with a non-finite g]; g is the gradient
-        the update read (after the exchange, the bf16 sums with the bf16 exchange, times grad_scale, unclipped -- the quantity grad_norm()
-        describes), p the parameter the next forward will use.  A step the device skipped (skip_nonfinite) leaves p unchanged and still
-        reports: `nonfinite_tensors(model)` names the tensors whose gradient went non-finite (it synchronises), `tensor_names(model)` the
-        rows.  A plain attribute like the others (anything but a bool raises ValueError when the step is taken), not in state_dict(); with
-        False a step launches and allocates exactly what it always did.  On / off is baked into a captured step (`prepare_replay()` raises
-        when it differs); its small buffers come from the first eager step with it on or from `stats_buffers()` and are dropped with the
-        arena, the sticky count with them."""
+    tensor_stats (default False; anything but a bool is invalid): True makes every step report per parameter tensor what the step did:
+        behind the update launches (and the EMA launch) of the step, ytvln_tensor_stats_stage1 and ytvln_tensor_stats_stage2 run over every
+        launch class's whole chunk table (8 bytes per parameter read, 6 with bf16 gradients).  `tensor_stats_report()` returns two device
+        views in arena order: rows [||g||, max |g|, ||p||, max |p|] over the finite elements and rows [non-finite elements of g, of p,
+        steps so far with a non-finite g]; g is the gradient the update read (after the exchange, the bf16 sums with the bf16 exchange,
+        times grad_scale, unclipped -- the quantity grad_norm() describes), p the parameter the next forward will use.  A step the device
+        skipped (skip_nonfinite) leaves p unchanged and still reports: `nonfinite_tensors(model)` names the tensors whose gradient went
+        non-finite (it synchronises), `tensor_names(model)` the rows.  Buffers: `stats_buffers()`; the sticky third count goes with them."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
         if lr < 0.0:
@@ -195,27 +216,22 @@ class AdamW(Optimizer):
         # torch.bfloat16 (set by data-parallel wrappers with the bf16 exchange): the update reads the bf16 exchange buffer (grad_bf16()),
         # not the fp32 arena.  Local accumulation stays fp32 either way.
         self.exchange_dtype = torch.float32
-        self.max_grad_norm = None   # global gradient-norm clipping (class docstring); plain attributes, never part of state_dict()
+        # the opt-in features (class docstring): plain attributes, never part of state_dict()
+        self.max_grad_norm = None   # global gradient-norm clipping
         self.skip_nonfinite = False
-        self._captured_clip = False  # the clipping settings recorded into the last captured step (False: nothing captured yet)
-        self.trust_ratio = False    # LAMB layer-wise trust ratio (class docstring); a plain attribute, never part of state_dict()
-        self._captured_lamb = None  # trust_ratio as recorded into the last captured step (None: nothing captured yet)
-        self.ema_decay = None       # EMA of the weights (class docstring); plain attributes, never part of state_dict()
+        self.trust_ratio = False    # LAMB layer-wise trust ratio
+        self.ema_decay = None       # EMA of the weights
         self.ema_warmup = False
         self.ema_updates = 0        # EMA updates taken (host count; advances on a device-skipped step as state[p]["step"] does)
-        self._captured_ema = None   # feature on / off as recorded into the last captured step (None: nothing captured yet)
-        self.tensor_stats = False   # per-tensor gradient / weight statistics (class docstring); a plain attribute, never part of state_dict()
-        self._captured_stats = None  # tensor_stats as recorded into the last captured step (None: nothing captured yet)
+        self.tensor_stats = False   # per-tensor gradient / weight statistics
+        self._captured = None       # the CaptureSettings recorded into the last captured step (None: nothing captured yet)
+        self._group_slot = 0        # group_update(): the next free slot of the clip partials in this step
         self._ema_swapped = False   # swap_ema(): the parameter arena currently holds the shadow weights
         self._ema_carry = {}        # id(param) -> shadow values waiting for the next arena (rebuild, load_ema)
 
     # ---- arena management -----------------------------------------------------------------------------------------
     def _members(self):
         return [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"] if p.grad is not None]
-
-    def flat_grads(self):
-        """The flat gradient arena (None before the first step): what a data-parallel wrapper all-reduces."""
-        return None if self._arena is None else self._arena["g"]
 
     def arena_layout(self) -> Dict[int, tuple]:
         return {} if self._arena is None else dict(self._arena["index"])
@@ -249,8 +265,7 @@ class AdamW(Optimizer):
                 st["exp_avg"] = flat["m"][o:o + n].view(p.shape)
                 st["exp_avg_sq"] = flat["v"][o:o + n].view(p.shape)
         self._stash_ema(old)
-        self._arena = dict(flat, index=index, ids=[id(p) for _, p in members], pb=None, pb_versions={}, gb=None, partials=None, clip=None,
-                           lamb=None, ema=None, stats=None)
+        self._arena = new_arena(flat, index, [id(p) for _, p in members])
         self._launch = None
         del old
         if self._ema_carry and self.ema_decay is not None and not torch.cuda.is_current_stream_capturing():
@@ -311,6 +326,40 @@ class AdamW(Optimizer):
         for _, table, n in tables:
             ops.grad_pack_bf16(self._arena["g"], gb, table, n)
 
+    # ---- what the opt-in features share ------------------------------------------------------------------------------
+    def capture_settings(self) -> CaptureSettings:
+        """The validated settings a captured step bakes in.  Raises ValueError for any invalid opt-in attribute."""
+        return CaptureSettings(self.clip_settings(), self.lamb_setting(), self.ema_setting() is not None, self.stats_setting())
+
+    def _arena_records(self) -> int:
+        """CHUNK records of the whole arena: what the per-record partials of the features are sized by."""
+        return sum((numel + CHUNK - 1) // CHUNK for _, numel in self._arena["index"].values())
+
+    def _feature_buffers(self, key, attr, accessor, alloc):
+        """The buffers `_arena[key]` of an opt-in feature, the one rule for all of them: None before the arena exists; allocated on first
+        use by `alloc(arena, device)` -- callers ask only with the feature on, and never while capturing, where the buffers would live in
+        the graph's pool --; dropped with the arena; not part of state_dict."""
+        a = self._arena
+        if a is None:
+            return None
+        if a[key] is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{attr} was switched on after the last eager step: take one eager step with it on (or call "
+                                   f"{accessor}()) before capturing, so that its buffers do not live in a graph's pool")
+            a[key] = alloc(a, a["g"].device)
+        return a[key]
+
+    def capture_buffers(self):
+        """Allocate now, eagerly, whatever the current settings need, so that nothing of it lives in a graph's pool: the bf16 exchange
+        buffer and the buffers of every feature that is on."""
+        now = self.capture_settings()
+        if self.exchange_dtype == torch.bfloat16:
+            self.grad_bf16()
+        for on, buffers in ((now.clip is not None, self.clip_buffers), (now.lamb, self.lamb_buffers), (now.ema, self.ema_buffers),
+                            (now.stats, self.stats_buffers)):
+            if on:
+                buffers()
+
     # ---- global gradient-norm clipping ------------------------------------------------------------------------------
     def clip_settings(self):
         """None with the feature off, else (max_norm as a float -- inf: measure only --, skip_nonfinite).  Raises ValueError for a
@@ -329,19 +378,16 @@ class AdamW(Optimizer):
 
     def clip_buffers(self):
         """(partials, clip): one fp32 partial per CHUNK record of the arena and the record [norm, coef, skip, skipped steps] the kernels
-        exchange.  Allocated on first use -- only with the feature on -- and dropped with the arena; not part of state_dict.  None before
-        the arena exists."""
-        a = self._arena
-        if a is None:
-            return None
-        if a["clip"] is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("gradient clipping was switched on after the last eager step: take one eager step with it on (or call "
-                                   "clip_buffers()) before capturing, so that its buffers do not live in a graph's pool")
-            n = sum((numel + CHUNK - 1) // CHUNK for _, numel in a["index"].values())
-            a["partials"] = torch.zeros(n, dtype=torch.float32, device=a["g"].device)
-            a["clip"] = torch.zeros(4, dtype=torch.float32, device=a["g"].device)
-        return a["partials"], a["clip"]
+        exchange (_feature_buffers: None before the arena exists)."""
+        def alloc(a, dev):
+            a["partials"] = torch.zeros(self._arena_records(), dtype=torch.float32, device=dev)
+            return torch.zeros(4, dtype=torch.float32, device=dev)
+        clip = self._feature_buffers("clip", "max_grad_norm / skip_nonfinite", "clip_buffers", alloc)
+        return None if clip is None else (self._arena["partials"], clip)
+
+    def _clip_record(self):
+        """The clip record when clipping is on, else None: what the clip-aware launches take."""
+        return self.clip_buffers()[1] if self.clip_settings() is not None else None
 
     def _grad_operand(self):
         """The gradient the update reads: the fp32 arena, or the bf16 sums of the bf16 exchange."""
@@ -394,21 +440,13 @@ class AdamW(Optimizer):
 
     def lamb_buffers(self):
         """(partials, trust, report): two fp32 partials per CHUNK record of the arena, one trust ratio and one report row
-        [||p||, ||r||, trust, 0] per arena tensor.  Allocated on first use -- only with trust_ratio on -- and dropped with the arena; not
-        part of state_dict.  None before the arena exists."""
-        a = self._arena
-        if a is None:
-            return None
-        if a["lamb"] is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("trust_ratio was switched on after the last eager step: take one eager step with it on (or call "
-                                   "lamb_buffers()) before capturing, so that its buffers do not live in a graph's pool")
-            dev, nt = a["g"].device, len(a["index"])
-            n = sum((numel + CHUNK - 1) // CHUNK for _, numel in a["index"].values())
-            a["lamb"] = (torch.zeros(2 * n, dtype=torch.float32, device=dev), torch.ones(nt, dtype=torch.float32, device=dev),
-                         torch.zeros(nt, 4, dtype=torch.float32, device=dev))
+        [||p||, ||r||, trust, 0] per arena tensor (_feature_buffers: None before the arena exists)."""
+        def alloc(a, dev):
+            n, nt = self._arena_records(), len(a["index"])
             a["lamb_stepped"] = False
-        return a["lamb"]
+            return (torch.zeros(2 * n, dtype=torch.float32, device=dev), torch.ones(nt, dtype=torch.float32, device=dev),
+                    torch.zeros(nt, 4, dtype=torch.float32, device=dev))
+        return self._feature_buffers("lamb", "trust_ratio", "lamb_buffers", alloc)
 
     def trust_ratios(self):
         """Device tensor [tensors in arena order (arena_layout()), 4]: the rows [||p||, ||r||, trust, 0] of the last LAMB step, the norms
@@ -422,7 +460,7 @@ class AdamW(Optimizer):
         """The three LAMB launches of launch class `c` on the current stream."""
         a = self._arena
         partials, trust, report = self.lamb_buffers()
-        clip = self.clip_buffers()[1] if self.clip_settings() is not None else None
+        clip = self._clip_record()
         part = partials[2 * c["rec0"]:2 * (c["rec0"] + c["n"])]
         ops.lamb_stage1(a["p"], self._grad_operand(), a["m"], a["v"], c["table"], c["n"], c["hyper"], part, self.grad_scale, clip)
         ops.lamb_trust(part, c["table"], c["n"], c["tensor_first"], c["rec_tensor"], c["ntensors"], trust, report, clip)
@@ -439,21 +477,14 @@ class AdamW(Optimizer):
     def stats_buffers(self):
         """(partials, bad, stats, counts): four fp32 partials and two int32 counts per CHUNK record of the arena, one report row
         [grad norm, max |g|, weight norm, max |p|] (fp32) and one row [non-finite g, non-finite p, steps with a non-finite g] (int64) per
-        arena tensor.  Allocated on first use -- only with tensor_stats on -- and dropped with the arena (the sticky third count restarts
-        with it, as skipped_steps() does); not part of state_dict.  None before the arena exists."""
-        a = self._arena
-        if a is None:
-            return None
-        if a["stats"] is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("tensor_stats was switched on after the last eager step: take one eager step with it on (or call "
-                                   "stats_buffers()) before capturing, so that its buffers do not live in a graph's pool")
-            dev, nt = a["g"].device, len(a["index"])
-            n = sum((numel + CHUNK - 1) // CHUNK for _, numel in a["index"].values())
-            a["stats"] = (torch.zeros(4 * n, dtype=torch.float32, device=dev), torch.zeros(2 * n, dtype=torch.int32, device=dev),
-                          torch.zeros(nt, 4, dtype=torch.float32, device=dev), torch.zeros(nt, 3, dtype=torch.int64, device=dev))
+        arena tensor (_feature_buffers: None before the arena exists; the sticky third count restarts with the arena, as skipped_steps()
+        does)."""
+        def alloc(a, dev):
+            n, nt = self._arena_records(), len(a["index"])
             a["stats_stepped"] = False
-        return a["stats"]
+            return (torch.zeros(4 * n, dtype=torch.float32, device=dev), torch.zeros(2 * n, dtype=torch.int32, device=dev),
+                    torch.zeros(nt, 4, dtype=torch.float32, device=dev), torch.zeros(nt, 3, dtype=torch.int64, device=dev))
+        return self._feature_buffers("stats", "tensor_stats", "stats_buffers", alloc)
 
     def tensor_stats_launch(self):
         """The two statistics launches of every launch class over its whole chunk table, on the current stream.  Belongs behind the step's
@@ -530,15 +561,12 @@ class AdamW(Optimizer):
         """The shadow arena: fp32, the size and offsets of the parameter arena.  Created on first use -- only with the feature on -- as a copy
         of the parameter arena at that moment; shadow values carried over from a previous arena or handed to load_ema() replace the copy for
         their parameters.  Not part of state_dict.  None before the arena exists."""
-        a = self._arena
-        if a is None:
-            return None
-        if a["ema"] is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("ema_decay was switched on after the last eager step: take one eager step with it on (or call "
-                                   "ema_buffers()) before capturing, so that its buffer does not live in a graph's pool")
+        def alloc(a, dev):
             with torch.no_grad():
-                a["ema"] = a["p"].clone()
+                return a["p"].clone()
+        a = self._arena
+        if self._feature_buffers("ema", "ema_decay", "ema_buffers", alloc) is None:
+            return None
         if self._ema_carry:
             with torch.no_grad():
                 for pid in [pid for pid in self._ema_carry if pid in a["index"]]:
@@ -655,7 +683,7 @@ class AdamW(Optimizer):
         shadow = self.ema_buffers() if self.ema_setting() is not None else None
         self._update_launches(table, n, hyper, cls)
         if shadow is not None:          # a launch of its own behind the update: element-wise, so any cut of the table will do
-            ops.ema_update(a["p"], shadow, table, n, hyper, self.clip_buffers()[1] if self.clip_settings() is not None else None)
+            ops.ema_update(a["p"], shadow, table, n, hyper, self._clip_record())
 
     def _update_launches(self, table, n, hyper, cls=None):
         a = self._arena
@@ -663,16 +691,23 @@ class AdamW(Optimizer):
             if cls is None or table is not cls["table"]:
                 raise RuntimeError("trust_ratio: the norms run over whole tensors, so the update runs over whole launch classes "
                                    "(launch_classes()), not over pieces of their chunk tables")
-            self._lamb_update(cls)
-        elif self.clip_settings() is not None:
-            ops.adamw_step_clip(a["p"], self._grad_operand(), a["m"], a["v"], table, n, hyper, self.clip_buffers()[1], self.grad_scale,
-                                p_bf16=a["pb"])
-        elif self.exchange_dtype == torch.bfloat16:
-            if a["gb"] is None:
-                raise RuntimeError("bf16 gradient exchange: the update would read a bf16 buffer nothing was packed into")
-            ops.adamw_step_gbf16(a["p"], a["gb"], a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
+            return self._lamb_update(cls)
+        g, clip = self._grad_operand(), self._clip_record()
+        if clip is not None:
+            ops.adamw_step_clip(a["p"], g, a["m"], a["v"], table, n, hyper, clip, self.grad_scale, p_bf16=a["pb"])
+        elif g.dtype == torch.bfloat16:
+            ops.adamw_step_gbf16(a["p"], g, a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
         else:
-            ops.adamw_step(a["p"], a["g"], a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
+            ops.adamw_step(a["p"], g, a["m"], a["v"], table, n, hyper, self.grad_scale, p_bf16=a["pb"])
+
+    def _adopt_grad(self, p):
+        """A member's gradient that is not the view of its arena slot (model.zero_grad() dropped the views; the few tensors autograd
+        allocates itself) is copied into the slot and becomes the view.  Callers hold torch.no_grad()."""
+        fg = self._arena["g"]
+        o, n = self._arena["index"][id(p)]
+        if p.grad.data_ptr() != fg.data_ptr() + 4 * o:
+            fg[o:o + n].copy_(p.grad.reshape(-1))
+            p.grad = fg[o:o + n].view(p.shape)
 
     def _ensure_arena(self):
         members = self._members()
@@ -681,18 +716,14 @@ class AdamW(Optimizer):
         if self._arena is None or self._arena["ids"] != [id(p) for _, p in members]:
             self._build_arena(members)
             return members
-        fp, fg, index = self._arena["p"], self._arena["g"], self._arena["index"]
-        base_p, base_g = fp.data_ptr(), fg.data_ptr()
+        base_p, index = self._arena["p"].data_ptr(), self._arena["index"]
         stale_data = False
         with torch.no_grad():
             for _, p in members:
-                o, n = index[id(p)]
-                if p.data_ptr() != base_p + 4 * o:
+                if p.data_ptr() != base_p + 4 * index[id(p)][0]:
                     stale_data = True
                     break
-                if p.grad.data_ptr() != base_g + 4 * o:       # e.g. model.zero_grad() dropped the views: re-adopt
-                    fg[o:o + n].copy_(p.grad.reshape(-1))
-                    p.grad = fg[o:o + n].view(p.shape)
+                self._adopt_grad(p)
         if stale_data:                                         # parameters were re-allocated (model.to(...)): rebuild
             self._build_arena(members)
         return members
@@ -707,13 +738,7 @@ class AdamW(Optimizer):
         rec0 = 0
         for (gi, step), plist in classes.items():
             wd = float(self.param_groups[gi]["weight_decay"])
-            rec = bytearray()
-            n = 0
-            for p in plist:
-                o, numel = index[id(p)]
-                for c in range(0, numel, CHUNK):
-                    rec += struct.pack("<qqff", o + c, min(CHUNK, numel - c), wd, 0.0)
-                    n += 1
+            rec, n = chunk_table([index[id(p)] + (wd,) for p in plist])
             table = torch.frombuffer(rec, dtype=torch.uint8).to(dev)
             first, rec_tensor = lamb_tables([(order[id(p)], index[id(p)][1]) for p in plist])
             assert len(rec_tensor) == n
@@ -771,15 +796,13 @@ class AdamW(Optimizer):
             self.ema_updates += 1
 
     def _launch_kernels(self):
-        if self.clip_settings() is not None:      # norm of what the update reads -> coefficient -> clip-aware update, all in stream order
+        now = self.capture_settings()
+        if now.clip is not None:                  # norm of what the update reads -> coefficient -> clip-aware update, all in stream order
             self.clip_coef(self.sumsq_tables([(ci, c["table"], c["n"]) for ci, c in enumerate(self._launch)], 0))
         if torch.cuda.is_current_stream_capturing():
-            self._captured_clip = self.clip_settings()
-            self._captured_lamb = self.lamb_setting()
-            self._captured_ema = self.ema_setting() is not None
-            self._captured_stats = self.stats_setting()
+            self._captured = now
         self.launch_classes()
-        if self.stats_setting():                  # behind every update and EMA launch of the step
+        if now.stats:                             # behind every update and EMA launch of the step
             self.tensor_stats_launch()
 
     @torch.no_grad()
@@ -788,18 +811,12 @@ class AdamW(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        self.clip_settings()              # invalid max_grad_norm: ValueError before anything is exchanged, launched or recorded
-        self.lamb_setting()               # (and an invalid trust_ratio)
-        self.ema_setting()                # (and an invalid ema_decay / ema_warmup)
-        self.stats_setting()              # (and an invalid tensor_stats)
+        self.capture_settings()           # an invalid opt-in attribute: ValueError before anything is exchanged, launched or recorded
         self._not_swapped("step()")
         if torch.cuda.is_current_stream_capturing():
             # inside a hipGraph capture of a whole training step: only the device work is recorded; the caller uploads the
             # hyper-parameters eagerly before every replay (`prepare_replay()`).  The arena must already exist.
-            if self._arena is None or self._launch is None:
-                raise RuntimeError("run at least one eager optimizer step before capturing a step into a graph")
-            if self._arena["ids"] != [id(p) for _, p in self._members()]:
-                raise RuntimeError("the set of parameters receiving gradients changed; cannot capture")
+            self._capture_ready("step()")
             self._ensure_arena()          # records the device copies that adopt the few non-arena gradients (embeddings)
             self._written.clear()
             self._launch_kernels()
@@ -819,33 +836,28 @@ class AdamW(Optimizer):
 
     # -- two-phase capture for data-parallel runs (ytvln.distributed.GraphedTrainStep): the gradient exchange sits between the
     #    "gradients are complete in the arena" point and the update, and stays outside any graph.
-    def capture_adopt(self):
-        """Inside a capture, after backward: record the copies that bring the few non-arena gradients into the flat arena."""
+    def _capture_ready(self, what, same_members=True):
+        """The preconditions of recording a step: a capture runs, an eager step built the arena, and (`same_members`) its members are unchanged."""
         if not torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("capture_adopt() is only meaningful while capturing a hipGraph")
+            raise RuntimeError(f"{what} is only meaningful while capturing a hipGraph")
         if self._arena is None or self._launch is None:
             raise RuntimeError("run at least one eager optimizer step before capturing a step into a graph")
-        if self._arena["ids"] != [id(p) for _, p in self._members()]:
+        if same_members and self._arena["ids"] != [id(p) for _, p in self._members()]:
             raise RuntimeError("the set of parameters receiving gradients changed; cannot capture")
+
+    def capture_adopt(self):
+        """Inside a capture, after backward: record the copies that bring the few non-arena gradients into the flat arena."""
+        self._capture_ready("capture_adopt()")
         self._ensure_arena()
 
     def capture_adopt_some(self, params):
         """Inside a capture, in the middle of a phased backward: bring the gradients of `params` (complete at this point, the others may
         not exist yet) into their arena slots -- the partial form of capture_adopt()."""
-        if not torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("capture_adopt_some() is only meaningful while capturing a hipGraph")
-        if self._arena is None or self._launch is None:
-            raise RuntimeError("run at least one eager optimizer step before capturing a step into a graph")
-        fg, index = self._arena["g"], self._arena["index"]
-        base_g = fg.data_ptr()
+        self._capture_ready("capture_adopt_some()", same_members=False)
         with torch.no_grad():
             for p in params:
-                if p.grad is None or id(p) not in index:
-                    continue
-                o, n = index[id(p)]
-                if p.grad.data_ptr() != base_g + 4 * o:
-                    fg[o:o + n].copy_(p.grad.reshape(-1))
-                    p.grad = fg[o:o + n].view(p.shape)
+                if p.grad is not None and id(p) in self._arena["index"]:
+                    self._adopt_grad(p)
 
     # -- the update in pieces (ytvln.distributed.GraphedTrainStep, phased): each group of arena ranges is updated as soon as ITS gradients are
     #    complete and exchanged, on the communication stream, under the rest of the backward pass.  The kernel is element-wise over a chunk
@@ -867,23 +879,19 @@ class AdamW(Optimizer):
                     return k
             return None
         out = [[] for _ in group_slices]
-        covered = 0
         for ci, c in enumerate(self._launch):
             wd = float(self.param_groups[c["group"]]["weight_decay"])
-            recs = [bytearray() for _ in group_slices]
-            counts = [0] * len(group_slices)
+            runs = [[] for _ in group_slices]
             for p in c["params"]:
                 o, numel = index[id(p)]
                 k = group_of(o)
                 if k is None:
                     raise RuntimeError("a parameter of the arena belongs to no gradient group: cannot split the update")
-                covered += numel
-                for ch in range(0, numel, CHUNK):
-                    recs[k] += struct.pack("<qqff", o + ch, min(CHUNK, numel - ch), wd, 0.0)
-                    counts[k] += 1
-            for k, rec in enumerate(recs):
-                if counts[k]:
-                    out[k].append((ci, torch.frombuffer(rec, dtype=torch.uint8).to(dev), counts[k]))
+                runs[k].append((o, numel, wd))
+            for k, r in enumerate(runs):
+                rec, n = chunk_table(r)
+                if n:
+                    out[k].append((ci, torch.frombuffer(rec, dtype=torch.uint8).to(dev), n))
         if owner is not None:
             owner._group_tables_cache = (self._launch, out)
         return out
@@ -900,8 +908,30 @@ class AdamW(Optimizer):
         for ci, table, n in tables:
             self._update(table, n, self._launch[ci]["hyper"])
 
-    def finish_group_step(self):
-        """After the last group of a step: gradients are consumed, arena slots may be written directly again."""
+    def group_update(self, tables_k):
+        """The gradients of one group (`tables_k`: its entry of group_tables()) are complete and exchanged: launch, on the current stream,
+        what can be done now.  Plain AdamW (with or without the EMA): the group's update.  With clipping on: only its sums of squares, into
+        the next free partial slots -- the coefficient needs every group's.  With the trust ratio on: nothing -- its launches run over
+        whole launch classes, which the groups cut across.  finish_group_step() does the rest."""
+        if self.clip_settings() is not None:
+            self._group_slot = self.sumsq_tables(tables_k, self._group_slot)
+        elif not self.lamb_setting():
+            self.launch_tables(tables_k)
+
+    def finish_group_step(self, tables):
+        """After group_update() of the last group of `tables` (group_tables()), on the current stream: the clip coefficient over the slots
+        the groups filled and every update they deferred (in group order, or per launch class with the trust ratio on), then the per-tensor
+        statistics behind the step's last update.  Gradients are consumed: arena slots may be written directly again."""
+        now = self.capture_settings()
+        if now.clip is not None:
+            self.clip_coef(self._group_slot)
+        if now.lamb:
+            self.launch_classes()
+        elif now.clip is not None:
+            for tables_k in tables:
+                self.launch_tables(tables_k)
+        if now.stats:
+            self.tensor_stats_launch()
         self._written.clear()
 
     def arena_range(self, p):
@@ -925,18 +955,14 @@ class AdamW(Optimizer):
         carries the clipping settings, trust_ratio, EMA on / off and tensor_stats it was recorded with: raises if one of them changed since
         (the EMA's decay and warm-up travel by value and may change freely)."""
         self._not_swapped("prepare_replay()")
-        if self._captured_clip is not False and self.clip_settings() != self._captured_clip:
-            raise RuntimeError(f"max_grad_norm / skip_nonfinite changed since the step was captured (captured {self._captured_clip}, now "
-                               f"{self.clip_settings()}): the graph holds the old launches -- capture the step again")
-        if self._captured_lamb is not None and self.lamb_setting() != self._captured_lamb:
-            raise RuntimeError(f"trust_ratio changed since the step was captured (captured {self._captured_lamb}, now {self.trust_ratio}): "
-                               "the graph holds the old launches -- capture the step again")
-        if self._captured_ema is not None and (self.ema_setting() is not None) != self._captured_ema:
-            raise RuntimeError(f"ema_decay was switched {'off' if self._captured_ema else 'on'} since the step was captured: "
-                               "the graph holds the old launches -- capture the step again")
-        if self._captured_stats is not None and self.stats_setting() != self._captured_stats:
-            raise RuntimeError(f"tensor_stats changed since the step was captured (captured {self._captured_stats}, now {self.tensor_stats}): "
-                               "the graph holds the old launches -- capture the step again")
+        if self._captured is not None:
+            now = self.capture_settings()
+            changed = [f"{_SETTING_ATTRS[f]} (captured {was!r}, now {is_!r})"
+                       for f, was, is_ in zip(now._fields, self._captured, now) if was != is_]
+            if changed:
+                raise RuntimeError(f"changed since the step was captured: {'; '.join(changed)}: the graph holds the old launches -- "
+                                   "capture the step again")
+        self._group_slot = 0
         self._upload_hyper()
 
     def zero_grad(self, set_to_none: bool = True):
