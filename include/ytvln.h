@@ -228,6 +228,49 @@ int ytvln_expand_ragged_f32(const float* pool_features,   /* [pool_rows, F]     
                             int64_t* bad,                 /* NULL or [1], accumulates */
                             void* stream);
 
+/* Raw-record frame pool (csrc/pool.hip): the pool holds decoded records as they come off the disk, frame p in rows
+ * offsets[p] .. offsets[p+1]-1 of pool_features [rows, F], pool_probs [rows, C] and
+ *   pool_geom [rows, 8] = x1, y1, x2, y2 (pixels), image width, image height of the row's record, featureHeading, featureElevation
+ * (0 where the store has none), and what the reference's readers compute on the host happens on the device.
+ *
+ * ytvln_pool_global_rows_f32: out_global[p, c] = (((0 + x[a, c]) + x[a+1, c]) + ... + x[b-1, c]) / (float)(b - a), a = offsets[p],
+ *   b = offsets[p+1], in fp32 and in ROW ORDER: numpy's order for mean(axis=0) of this layout, and part of the contract.  Zero for an
+ *   empty frame and for offsets out of order or out of range; nothing outside rows [0, pool_rows) is read.
+ *
+ * ytvln_expand_records_f32: the outputs, the work split and the "every output element written exactly once" rule of
+ *   ytvln_expand_ragged_f32.  A slot showing frame p with n_src rows has n = min(n_src + 1, boxes) real rows:
+ *   row 0 = the global region: features pool_global[p], probs (float)(1.0 / C), boxes [0,0,1,1,1, 0,1,0,1,0,1], or with `view`
+ *     [0,0,1,1,1, sin(-h), cos(-h), 0, 1, sin(-nh), cos(-nh)] (h, nh = view[s, 0], view[s, 1]; double, rounded once to fp32);
+ *   rows 1 .. n-1 = source rows 0 .. n-2: features and probs copied, box columns 0-3 = x1/w, y1/h, x2/w, y2/h, column 4 =
+ *     ((x2-x1)*(y2-y1)) / (w*h), all fp32 with correctly rounded division; columns 5-10 = 1, or with `view`
+ *     sin(d1), cos(d1), sin(fe), cos(fe), sin(d2), cos(d2) with d1 = fh - (float)h, d2 = fh - (float)nh in fp32, the functions in double
+ *     on the fp32 argument, rounded once;
+ *   rows n .. boxes-1 and padding slots (index -1): exact zeros, mask 0; column 11 = slot % frames for every row of every slot.
+ *   BAD slot (all padding, bad[0] += 1): index out of range, offsets out of order or out of range, or an EMPTY frame.  The range check
+ *   on the frame precedes the read of its offsets, the offsets check any read of a row or of pool_global.
+ * Both: no allocation, no host synchronisation, capturable; invalid arguments (as for ytvln_expand_ragged_f32) return a negative code
+ * and launch nothing. */
+int ytvln_pool_global_rows_f32(const float* pool_features,   /* [pool_rows, F]                             */
+                               const int64_t* offsets,       /* [pool_frames + 1], first row of each frame */
+                               int64_t pool_frames, int64_t pool_rows, int F,
+                               float* out_global,            /* [pool_frames, F]                           */
+                               void* stream);
+int ytvln_expand_records_f32(const float* pool_features,   /* [pool_rows, F]                                   */
+                             const float* pool_geom,       /* [pool_rows, 8]                                   */
+                             const float* pool_probs,      /* [pool_rows, C] or NULL (then out_probs NULL too) */
+                             const float* pool_global,     /* [pool_frames, F] from ytvln_pool_global_rows_f32 */
+                             const int64_t* offsets,       /* [pool_frames + 1]                                */
+                             int64_t pool_frames, int64_t pool_rows,
+                             const int64_t* index,         /* [slots], -1 = padding                            */
+                             const double* view,           /* [slots, 2] heading, next heading, or NULL        */
+                             int64_t slots, int frames, int boxes, int F, int C,
+                             float* out_features,          /* [slots * boxes, F]  */
+                             float* out_boxes,             /* [slots * boxes, 12] */
+                             float* out_probs,             /* [slots * boxes, C] or NULL */
+                             int64_t* out_masks,           /* [slots * boxes]     */
+                             int64_t* bad,                 /* NULL or [1], accumulates */
+                             void* stream);
+
 /* out[j, :] = x[idx[j], :] (zeros where idx[j] < 0): row gather in front of the loss-aware prediction heads (only rows that
  * carry a masked-language / masked-vision target are decoded; "next" row of SURVEY.md section 8f).  Backward =
  * ytvln_scatter_add_rows_f32 with skip_idx = -1. */

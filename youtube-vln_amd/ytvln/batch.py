@@ -9,6 +9,9 @@ sits in HBM.  The loader then only has to ship the un-masked tokens / features /
     expand_options(pool..., index)                   -> items 1, 2, 4, 3 from a pool padded to `boxes` rows per frame
     expand_ragged(pool..., offsets, index, boxes)    -> the same from the un-padded rows the feature readers return, in one launch
     RaggedPool(capacity_rows, capacity_frames)       pinned staging + static device buffers around expand_ragged
+    global_rows(pool_features, offsets)              -> the readers' global (mean) feature row of every pool frame, numpy's summation order
+    expand_records(pool..., offsets, index, boxes)   -> expand_ragged from RAW records: global region, box geometry, headings on the device
+    RecordPool(capacity_rows, capacity_frames)       pinned staging + static device buffers around global_rows + expand_records
 
 Draws come from the library's Philox stream (`ops.DropoutState`: seed + device-side counter, so the masks change every call and
 replay inside a hipGraph); passing `p=` / `random_tokens=` (/ `action_choice=`) reproduces the reference functions bit for bit (tests).
@@ -22,6 +25,7 @@ from __future__ import annotations
 
 import math
 import struct
+import warnings
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -172,6 +176,62 @@ def _want(t, name: str, dtype, shape) -> None:
         raise ValueError(f"ytvln.batch: `{name}` must be contiguous")
 
 
+def _check_pool(boxes, pool_features, per_row, pool_probs, offsets, index):
+    """The checks expand_ragged and expand_records share on their inputs (ValueError, nothing touched).  `per_row` = [(name, tensor, columns
+    or None)]: the fp32 tensors that hold one row per row of `pool_features`.  Returns (boxes, rows, F, C, (bs, K, frames))."""
+    boxes = int(boxes)
+    if boxes <= 0:
+        raise ValueError(f"ytvln.batch: boxes must be positive, got {boxes}")
+    _want(pool_features, "pool_features", torch.float32, (None, None))
+    rows, F = pool_features.shape
+    for name, t, cols in per_row:
+        _want(t, name, torch.float32, (rows, cols))
+    C = 0
+    if pool_probs is not None:
+        _want(pool_probs, "pool_probs", torch.float32, (rows, None))
+        C = pool_probs.shape[1]
+    _want(offsets, "offsets", torch.int64, (None,))
+    if offsets.numel() < 1:
+        raise ValueError("ytvln.batch: `offsets` holds one entry per pool frame plus one")
+    _want(index, "index", torch.int64, (None, None, None))
+    if index.shape[2] <= 0:
+        raise ValueError("ytvln.batch: `index` [bs, K, frames] needs frames >= 1")
+    return boxes, rows, F, C, tuple(index.shape)
+
+
+def _check_out(who: str, inputs, out, bad, lead, F: int, C: int):
+    """The second half of those checks: `out` and `bad` (ValueError), then every tensor on the GPU (RuntimeError) and on one device.
+    `inputs` = [(name, tensor or None)], `pool_features` first and `pool_probs` among them; `lead` = (bs, K, frames * boxes).  Returns the
+    four output tensors, allocated here when `out` is None."""
+    probs = dict(inputs)["pool_probs"] is not None
+    if out is not None:
+        if len(out) != 4:
+            raise ValueError("ytvln.batch: `out` is (image_features, image_boxes, image_probs, image_masks)")
+        f, bx, pr, m = out
+        _want(f, "out[0]", torch.float32, (*lead, F))
+        _want(bx, "out[1]", torch.float32, (*lead, 12))
+        if (pr is None) == probs:
+            raise ValueError("ytvln.batch: out[2] (image_probs) and `pool_probs` go together: both given or both None")
+        if pr is not None:
+            _want(pr, "out[2]", torch.float32, (*lead, C))
+        _want(m, "out[3]", torch.int64, lead)
+    if bad is not None:
+        _want(bad, "bad", torch.int64, (1,))
+    tensors = list(inputs) + [("bad", bad)] + ([(f"out[{i}]", t) for i, t in enumerate(out)] if out is not None else [])
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"ytvln.batch: `{name}` must live on the GPU (no CPU path)")
+    dev = inputs[0][1].device
+    if any(t is not None and t.device != dev for _, t in tensors):
+        raise ValueError(f"ytvln.batch: {who} needs all its tensors on one device")
+    if out is None:
+        f = torch.empty(*lead, F, dtype=torch.float32, device=dev)
+        bx = torch.empty(*lead, 12, dtype=torch.float32, device=dev)
+        pr = torch.empty(*lead, C, dtype=torch.float32, device=dev) if probs else None
+        m = torch.empty(*lead, dtype=torch.int64, device=dev)
+    return f, bx, pr, m
+
+
 def expand_ragged(pool_features: Tensor, pool_locations: Tensor, pool_probs: Optional[Tensor], offsets: Tensor, index: Tensor, boxes: int,
                   out: Optional[Sequence[Optional[Tensor]]] = None, bad: Optional[Tensor] = None):
     """Padding, masks and option expansion from a RAGGED frame pool in one launch (`ytvln_expand_ragged_f32`).  The pool holds what the
@@ -189,105 +249,103 @@ def expand_ragged(pool_features: Tensor, pool_locations: Tensor, pool_probs: Opt
     Column 11 of the boxes is the position of the frame inside its option for EVERY row, padding frames included, which is what the
     reference writes (`all_dataset.py:314` and `:331`); `expand_options` writes 0 for padding frames.  The difference is confined to
     rows behind a zero mask.  Shapes and dtypes are checked first (ValueError, nothing touched); there is no CPU path."""
-    boxes = int(boxes)
-    if boxes <= 0:
-        raise ValueError(f"ytvln.batch: boxes must be positive, got {boxes}")
-    _want(pool_features, "pool_features", torch.float32, (None, None))
-    rows, F = pool_features.shape
-    _want(pool_locations, "pool_locations", torch.float32, (rows, None))
+    boxes, rows, F, C, (bs, K, frames) = _check_pool(boxes, pool_features, [("pool_locations", pool_locations, None)], pool_probs, offsets, index)
     L = pool_locations.shape[1]
     if L > 11:
         raise ValueError(f"ytvln.batch: `pool_locations` has {L} columns; the boxes hold 11 next to the position column")
-    C = 0
-    if pool_probs is not None:
-        _want(pool_probs, "pool_probs", torch.float32, (rows, None))
-        C = pool_probs.shape[1]
-    _want(offsets, "offsets", torch.int64, (None,))
-    if offsets.numel() < 1:
-        raise ValueError("ytvln.batch: `offsets` holds one entry per pool frame plus one")
-    _want(index, "index", torch.int64, (None, None, None))
-    bs, K, frames = index.shape
-    if frames <= 0:
-        raise ValueError("ytvln.batch: `index` [bs, K, frames] needs frames >= 1")
-    R = frames * boxes
-    if out is not None:
-        if len(out) != 4:
-            raise ValueError("ytvln.batch: `out` is (image_features, image_boxes, image_probs, image_masks)")
-        f, bx, pr, m = out
-        _want(f, "out[0]", torch.float32, (bs, K, R, F))
-        _want(bx, "out[1]", torch.float32, (bs, K, R, 12))
-        if (pr is None) != (pool_probs is None):
-            raise ValueError("ytvln.batch: out[2] (image_probs) and `pool_probs` go together: both given or both None")
-        if pr is not None:
-            _want(pr, "out[2]", torch.float32, (bs, K, R, C))
-        _want(m, "out[3]", torch.int64, (bs, K, R))
-    if bad is not None:
-        _want(bad, "bad", torch.int64, (1,))
-    tensors = [("pool_features", pool_features), ("pool_locations", pool_locations), ("pool_probs", pool_probs), ("offsets", offsets),
-               ("index", index), ("bad", bad)] + ([(f"out[{i}]", t) for i, t in enumerate(out)] if out is not None else [])
-    for name, t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"ytvln.batch: `{name}` must live on the GPU (no CPU path)")
-    dev = pool_features.device
-    if any(t is not None and t.device != dev for _, t in tensors):
-        raise ValueError("ytvln.batch: expand_ragged needs all its tensors on one device")
-    if out is None:
-        f = torch.empty(bs, K, R, F, dtype=torch.float32, device=dev)
-        bx = torch.empty(bs, K, R, 12, dtype=torch.float32, device=dev)
-        pr = torch.empty(bs, K, R, C, dtype=torch.float32, device=dev) if pool_probs is not None else None
-        m = torch.empty(bs, K, R, dtype=torch.int64, device=dev)
+    f, bx, pr, m = _check_out("expand_ragged", [("pool_features", pool_features), ("pool_locations", pool_locations), ("pool_probs", pool_probs),
+                                                ("offsets", offsets), ("index", index)], out, bad, (bs, K, frames * boxes), F, C)
     call("ytvln_expand_ragged_f32", ops._ptr(pool_features), ops._ptr(pool_locations), ops._ptr(pool_probs), ops._ptr(offsets),
          offsets.numel() - 1, rows, ops._ptr(index), bs * K * frames, frames, boxes, F, L, C, ops._ptr(f), ops._ptr(bx), ops._ptr(pr),
          ops._ptr(m), ops._ptr(bad), ops._stream())
     return f, bx, pr, m
 
 
-class RaggedPool:
-    """The frames of one step as the feature readers return them, shipped once: pinned host staging buffers and static device buffers of
-    fixed capacity, allocated here and reused every step.
+def global_rows(pool_features: Tensor, offsets: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The global feature row of every pool frame (`ytvln_pool_global_rows_f32`): out[p] = the fp32 sum of rows offsets[p] .. offsets[p+1]-1
+    of `pool_features` [rows, F], taken strictly in row order, divided by fp32(rows of the frame) -- bit for bit what the reference's readers
+    compute with `features.mean(axis=0)` (`features_reader.py:170`).  Zero for an empty frame and for offsets out of order or out of range.
+    `out` (fp32 [frames_in_pool, F], contiguous) is overwritten when given.  Shapes and dtypes are checked first; there is no CPU path."""
+    _want(pool_features, "pool_features", torch.float32, (None, None))
+    rows, F = pool_features.shape
+    _want(offsets, "offsets", torch.int64, (None,))
+    if offsets.numel() < 1:
+        raise ValueError("ytvln.batch: `offsets` holds one entry per pool frame plus one")
+    P = offsets.numel() - 1
+    if out is not None:
+        _want(out, "out", torch.float32, (P, F))
+    tensors = [("pool_features", pool_features), ("offsets", offsets), ("out", out)]
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"ytvln.batch: `{name}` must live on the GPU (no CPU path)")
+    dev = pool_features.device
+    if any(t is not None and t.device != dev for _, t in tensors):
+        raise ValueError("ytvln.batch: global_rows needs all its tensors on one device")
+    if out is None:
+        out = torch.empty(P, F, dtype=torch.float32, device=dev)
+    call("ytvln_pool_global_rows_f32", ops._ptr(pool_features), ops._ptr(offsets), P, rows, F, ops._ptr(out), ops._stream())
+    return out
 
-        pool = RaggedPool(capacity_rows, capacity_frames)
-        ids  = [pool.add(key, *reader[key], max_rows=boxes) for key in ...]      # one frame each; a key seen before costs nothing
-        idx  = pool.index(options, frames)                                         # nested lists of ids -> int64 [bs, K, frames]
-        pool.upload()                                                              # the used rows only, non-blocking, current stream
-        f, bx, pr, m = pool.expand(idx, boxes, out=static_inputs)                  # one launch (expand_ragged)
-        pool.reset()                                                               # next step
 
-    `add` converts fp64 arrays (the readers' locations and probabilities) to fp32 exactly as the reference's `.float()` does.  The device
-    buffers never move, so a captured `expand` replays on whatever the last `upload()` brought.  `reset()` waits for the last upload's
-    copies before the staging buffers are written again.  Without a GPU the object still does its host bookkeeping (tests); `upload` and
-    `expand` then raise."""
+def expand_records(pool_features: Tensor, pool_geom: Tensor, pool_probs: Optional[Tensor], pool_global: Tensor, offsets: Tensor, index: Tensor,
+                   boxes: int, view: Optional[Tensor] = None, out: Optional[Sequence[Optional[Tensor]]] = None, bad: Optional[Tensor] = None):
+    """`expand_ragged` for a pool of RAW records (`ytvln_expand_records_f32`): the pool holds what comes off the disk, and what the
+    reference's readers compute per frame on the host (`features_reader.py:91-124`, `:153-179`, `:258-341`) is done in the same launch:
 
-    def __init__(self, capacity_rows: int, capacity_frames: int, feature_dim: int = 2048, loc_dim: int = 11, num_classes: int = 1601,
-                 device=None, probs: bool = True):
+        pool_features [rows, F] fp32   pool_probs [rows, C] fp32 or None   offsets [frames_in_pool + 1] int64   index [bs, K, frames] int64
+        pool_geom   [rows, 8] fp32: x1, y1, x2, y2 in pixels, image width and height of the row's record, featureHeading, featureElevation
+        pool_global [frames_in_pool, F] fp32: `global_rows(pool_features, offsets)`
+        view        None, or fp64 [bs, K, frames, 2]: the agent's heading and next heading at each slot (the panorama reader's query)
+
+    A slot showing a frame of n rows gets min(n + 1, boxes) real rows: the global region first (mean feature, whole-image box, uniform
+    class distribution), then the frame's rows with their boxes normalised by the image size, the relative area in column 4 and, in
+    columns 5-10, ones (`view` None) or the sines and cosines of featureHeading - heading, featureElevation and featureHeading - next
+    heading.  Everything but those six columns equals the readers' output after `.float()` bit for bit; they are the fp64 functions of the
+    fp32 angle rounded once.  The headings being a per-slot input, one viewpoint is one pool frame under whatever headings it is seen.
+
+    Returns, `out` and `bad` as for `expand_ragged`; an EMPTY frame is a bad slot here (the readers raise for it).  Shapes and dtypes are
+    checked first (ValueError, nothing touched); there is no CPU path."""
+    boxes, rows, F, C, (bs, K, frames) = _check_pool(boxes, pool_features, [("pool_geom", pool_geom, 8)], pool_probs, offsets, index)
+    _want(pool_global, "pool_global", torch.float32, (offsets.numel() - 1, F))
+    if view is not None:
+        _want(view, "view", torch.float64, (bs, K, frames, 2))
+    if pool_probs is not None and C == 0:
+        raise ValueError("ytvln.batch: `pool_probs` needs at least one class (the global region holds 1 / C)")
+    f, bx, pr, m = _check_out("expand_records", [("pool_features", pool_features), ("pool_geom", pool_geom), ("pool_probs", pool_probs),
+                                                 ("pool_global", pool_global), ("offsets", offsets), ("index", index), ("view", view)],
+                              out, bad, (bs, K, frames * boxes), F, C)
+    call("ytvln_expand_records_f32", ops._ptr(pool_features), ops._ptr(pool_geom), ops._ptr(pool_probs), ops._ptr(pool_global),
+         ops._ptr(offsets), offsets.numel() - 1, rows, ops._ptr(index), ops._ptr(view), bs * K * frames, frames, boxes, F, C, ops._ptr(f),
+         ops._ptr(bx), ops._ptr(pr), ops._ptr(m), ops._ptr(bad), ops._stream())
+    return f, bx, pr, m
+
+
+class _FramePool:
+    """What RaggedPool and RecordPool share: per-row fp32 buffers `host_<name>` (pinned staging) / `<name>` (static device buffer) for every
+    (name, columns) of `_columns`, `offsets`, `bad`, keys -> ids, `index`, `upload` and `reset`.  The subclasses say which arrays a frame
+    consists of (`add`) and which kernels expand it (`expand`)."""
+
+    def __init__(self, capacity_rows: int, capacity_frames: int, columns, device=None):
+        kind = type(self).__name__
         capacity_rows, capacity_frames = int(capacity_rows), int(capacity_frames)
         if capacity_rows < 1 or capacity_frames < 1:
-            raise ValueError(f"ytvln.batch: RaggedPool capacities must be positive, got {capacity_rows} rows, {capacity_frames} frames")
-        if not 0 <= int(loc_dim) <= 11:
-            raise ValueError(f"ytvln.batch: loc_dim must be within [0, 11], got {loc_dim}")
+            raise ValueError(f"ytvln.batch: {kind} capacities must be positive, got {capacity_rows} rows, {capacity_frames} frames")
         self.capacity_rows, self.capacity_frames = capacity_rows, capacity_frames
-        self.feature_dim, self.loc_dim, self.num_classes = int(feature_dim), int(loc_dim), int(num_classes)
         if device is None and torch.cuda.is_available():
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device) if device is not None else None
         if self.device is not None and self.device.type != "cuda":
-            raise RuntimeError(f"ytvln.batch: RaggedPool's device buffers must live on the GPU (no CPU path), got {self.device}")
+            raise RuntimeError(f"ytvln.batch: {kind}'s device buffers must live on the GPU (no CPU path), got {self.device}")
         pin = self.device is not None
-
-        def host(*shape, dtype=torch.float32):
-            return torch.zeros(*shape, dtype=dtype, pin_memory=pin)
-
-        self.host_features = host(capacity_rows, self.feature_dim)
-        self.host_locations = host(capacity_rows, self.loc_dim)
-        self.host_probs = host(capacity_rows, self.num_classes) if probs else None
-        self.host_offsets = host(capacity_frames + 1, dtype=torch.int64)
-        self.features = self.locations = self.probs = self.offsets = self.bad = None
+        self._columns = [(name, int(cols)) for name, cols in columns if cols is not None]
+        for name, cols in columns:
+            setattr(self, "host_" + name, torch.zeros(capacity_rows, int(cols), pin_memory=pin) if cols is not None else None)
+            setattr(self, name, torch.zeros(capacity_rows, int(cols), device=self.device) if cols is not None and pin else None)
+        self.host_offsets = torch.zeros(capacity_frames + 1, dtype=torch.int64, pin_memory=pin)
+        self.offsets = self.bad = None
         if self.device is not None:
-            self.features = torch.zeros(capacity_rows, self.feature_dim, device=self.device)
-            self.locations = torch.zeros(capacity_rows, self.loc_dim, device=self.device)
-            self.probs = torch.zeros(capacity_rows, self.num_classes, device=self.device) if probs else None
             self.offsets = torch.zeros(capacity_frames + 1, dtype=torch.int64, device=self.device)
-            self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)        # slots with an out-of-range index, summed over the calls
+            self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)        # bad slots (see the expansion), summed over the calls
         self.rows = self.frames = 0
         self.bytes_uploaded = 0
         self._ids = {}
@@ -295,38 +353,33 @@ class RaggedPool:
 
     @staticmethod
     def _rows_of(x, name: str, cols: int, n: int) -> Tensor:
-        t = x if torch.is_tensor(x) else torch.from_numpy(x)
+        if torch.is_tensor(x):
+            t = x
+        else:
+            with warnings.catch_warnings():         # decoded records are read-only views of the store's bytes; they are only read here
+                warnings.simplefilter("ignore", UserWarning)
+                t = torch.from_numpy(x)
         if t.dim() != 2 or t.shape[1] < cols or t.dtype not in (torch.float32, torch.float64):
             raise ValueError(f"ytvln.batch: `{name}` must be an fp32 or fp64 array [n, {cols}], got {t.dtype} {list(t.shape)}")
         return t[:n, :cols]
 
-    def add(self, key, features, locations, probs=None, max_rows: Optional[int] = None) -> int:
-        """Append one frame (the tuple a reader's `__getitem__` returns) and return its pool id.  A key seen since the last `reset()`
-        returns its id and copies nothing.  `max_rows` keeps the first rows only (`num_boxes = min(len, max_num_boxes)`)."""
-        known = self._ids.get(key)
-        if known is not None:
-            return known
-        n = int(features.shape[0])
-        if max_rows is not None:
-            n = min(n, int(max_rows))
-        if (probs is None) != (self.host_probs is None):
-            raise ValueError("ytvln.batch: this RaggedPool was built with probs=%s" % (self.host_probs is not None))
-        f = self._rows_of(features, "features", self.feature_dim, n)
-        loc = self._rows_of(locations, "locations", self.loc_dim, n)
-        pr = self._rows_of(probs, "probs", self.num_classes, n) if probs is not None else None
-        if f.shape[1] != self.feature_dim or (pr is not None and pr.shape[1] != self.num_classes):
-            raise ValueError("ytvln.batch: feature / class width does not match the pool")
-        if loc.shape[0] != n or f.shape[0] != n or (pr is not None and pr.shape[0] != n):
-            raise ValueError(f"ytvln.batch: features, locations and probs of a frame need the same number of rows (>= {n} here)")
+    def _append(self, key, n: int, arrays) -> int:
+        """Copy the first `n` rows of every (name, array) of one frame behind the rows in use and return the frame's id.  Nothing is written
+        before every check has passed."""
+        kind = type(self).__name__
+        given = dict(arrays)
+        if any((given.get(name) is None) != (getattr(self, "host_" + name) is None) for name in given):
+            raise ValueError(f"ytvln.batch: this {kind} was built with probs={self.host_probs is not None}")
+        cut = [(name, self._rows_of(given[name], name, cols, n)) for name, cols in self._columns]
+        if any(t.shape[0] != n for _, t in cut):
+            raise ValueError(f"ytvln.batch: {', '.join(name for name, _ in cut)} of a frame need the same number of rows (>= {n} here)")
         if self.frames + 1 > self.capacity_frames:
-            raise ValueError(f"ytvln.batch: RaggedPool is full: capacity_frames = {self.capacity_frames}")
+            raise ValueError(f"ytvln.batch: {kind} is full: capacity_frames = {self.capacity_frames}")
         if self.rows + n > self.capacity_rows:
-            raise ValueError(f"ytvln.batch: {self.rows} + {n} rows exceed RaggedPool's capacity_rows = {self.capacity_rows}")
+            raise ValueError(f"ytvln.batch: {self.rows} + {n} rows exceed {kind}'s capacity_rows = {self.capacity_rows}")
         a, b = self.rows, self.rows + n
-        self.host_features[a:b].copy_(f)            # fp64 -> fp32 by copy_: the rounding of `.float()`
-        self.host_locations[a:b].copy_(loc)
-        if pr is not None:
-            self.host_probs[a:b].copy_(pr)
+        for name, t in cut:
+            getattr(self, "host_" + name)[a:b].copy_(t)            # fp64 -> fp32 by copy_: the rounding of `.float()`
         pid = self.frames
         self.frames, self.rows = pid + 1, b
         self.host_offsets[pid + 1] = b
@@ -351,7 +404,7 @@ class RaggedPool:
 
     def _need_device(self, what: str) -> None:
         if self.device is None:
-            raise RuntimeError(f"ytvln.batch: RaggedPool.{what} needs the GPU (no CPU path)")
+            raise RuntimeError(f"ytvln.batch: {type(self).__name__}.{what} needs the GPU (no CPU path)")
 
     def upload(self) -> None:
         """Non-blocking copies of the used prefix of each buffer, and of `offsets`, to the device on the current stream.  Entries of
@@ -359,10 +412,8 @@ class RaggedPool:
         self._need_device("upload")
         self.host_offsets[self.frames + 1:] = self.rows
         moved = 0
-        pairs = [(self.features, self.host_features), (self.locations, self.host_locations)]
-        if self.host_probs is not None:
-            pairs.append((self.probs, self.host_probs))
-        for d, h in pairs:
+        for name, _ in self._columns:
+            d, h = getattr(self, name), getattr(self, "host_" + name)
             if self.rows:
                 d[:self.rows].copy_(h[:self.rows], non_blocking=True)
             moved += self.rows * h.shape[1] * h.element_size()
@@ -372,13 +423,6 @@ class RaggedPool:
         self._uploaded = torch.cuda.Event()
         self._uploaded.record()
 
-    def expand(self, index: Tensor, boxes: int, out=None):
-        """`expand_ragged` on the device buffers (a CPU `index` is uploaded first)."""
-        self._need_device("expand")
-        if torch.is_tensor(index) and not index.is_cuda:
-            index = index.to(self.device, non_blocking=True)
-        return expand_ragged(self.features, self.locations, self.probs, self.offsets, index, boxes, out=out, bad=self.bad)
-
     def reset(self) -> None:
         """Start the next step: forget the frames and keys (the buffers stay)."""
         if self._uploaded is not None:
@@ -386,6 +430,98 @@ class RaggedPool:
             self._uploaded = None
         self.rows = self.frames = 0
         self._ids = {}
+
+
+class RaggedPool(_FramePool):
+    """The frames of one step as the feature readers return them, shipped once: pinned host staging buffers and static device buffers of
+    fixed capacity, allocated here and reused every step.
+
+        pool = RaggedPool(capacity_rows, capacity_frames)
+        ids  = [pool.add(key, *reader[key], max_rows=boxes) for key in ...]      # one frame each; a key seen before costs nothing
+        idx  = pool.index(options, frames)                                         # nested lists of ids -> int64 [bs, K, frames]
+        pool.upload()                                                              # the used rows only, non-blocking, current stream
+        f, bx, pr, m = pool.expand(idx, boxes, out=static_inputs)                  # one launch (expand_ragged)
+        pool.reset()                                                               # next step
+
+    `add` converts fp64 arrays (the readers' locations and probabilities) to fp32 exactly as the reference's `.float()` does.  The device
+    buffers never move, so a captured `expand` replays on whatever the last `upload()` brought.  `reset()` waits for the last upload's
+    copies before the staging buffers are written again.  Without a GPU the object still does its host bookkeeping (tests); `upload` and
+    `expand` then raise."""
+
+    def __init__(self, capacity_rows: int, capacity_frames: int, feature_dim: int = 2048, loc_dim: int = 11, num_classes: int = 1601,
+                 device=None, probs: bool = True):
+        if not 0 <= int(loc_dim) <= 11:
+            raise ValueError(f"ytvln.batch: loc_dim must be within [0, 11], got {loc_dim}")
+        self.feature_dim, self.loc_dim, self.num_classes = int(feature_dim), int(loc_dim), int(num_classes)
+        super().__init__(capacity_rows, capacity_frames, [("features", self.feature_dim), ("locations", self.loc_dim),
+                                                          ("probs", self.num_classes if probs else None)], device)
+
+    def add(self, key, features, locations, probs=None, max_rows: Optional[int] = None) -> int:
+        """Append one frame (the tuple a reader's `__getitem__` returns) and return its pool id.  A key seen since the last `reset()`
+        returns its id and copies nothing.  `max_rows` keeps the first rows only (`num_boxes = min(len, max_num_boxes)`)."""
+        known = self._ids.get(key)
+        if known is not None:
+            return known
+        n = int(features.shape[0])
+        if max_rows is not None:
+            n = min(n, int(max_rows))
+        return self._append(key, n, [("features", features), ("locations", locations), ("probs", probs)])
+
+    def expand(self, index: Tensor, boxes: int, out=None):
+        """`expand_ragged` on the device buffers (a CPU `index` is uploaded first)."""
+        self._need_device("expand")
+        if torch.is_tensor(index) and not index.is_cuda:
+            index = index.to(self.device, non_blocking=True)
+        return expand_ragged(self.features, self.locations, self.probs, self.offsets, index, boxes, out=out, bad=self.bad)
+
+
+class RecordPool(_FramePool):
+    """RaggedPool for RAW records: the frames of one step as they come off the disk (`reader.records(query)` / `reader.record(key)`:
+    features, geometry, probabilities, all fp32), shipped once; the global region, the box normalisation and the orientation columns are
+    computed on the device (`global_rows` + `expand_records`), so the host only decodes.
+
+        pool = RecordPool(capacity_rows, capacity_frames)
+        ids  = [pool.add(key, *reader.records(key)) for key in ...]                # ALL rows of the frame: the mean runs over every region
+        idx  = pool.index(options, frames)
+        pool.upload()
+        f, bx, pr, m = pool.expand(idx, boxes, view=headings, out=static_inputs)   # two launches on the current stream
+        pool.reset()
+
+    A panorama viewpoint is one frame whatever headings it is seen under: the headings are `view` (fp64 [bs, K, frames, 2]), not part of
+    the key.  The device buffers never move, so a captured `expand` replays on whatever the last `upload()` brought (and on whatever the
+    static `index` / `view` tensors hold).  Lifecycle, `bad` and the behaviour without a GPU are RaggedPool's."""
+
+    def __init__(self, capacity_rows: int, capacity_frames: int, feature_dim: int = 2048, num_classes: int = 1601, device=None,
+                 probs: bool = True):
+        self.feature_dim, self.num_classes = int(feature_dim), int(num_classes)
+        super().__init__(capacity_rows, capacity_frames, [("features", self.feature_dim), ("geom", 8),
+                                                          ("probs", self.num_classes if probs else None)], device)
+        self.global_features = None                 # [capacity_frames, F]: written by every expand() ahead of the expansion
+        if self.device is not None:
+            self.global_features = torch.zeros(self.capacity_frames, self.feature_dim, device=self.device)
+
+    def add(self, key, features, geom, probs=None) -> int:
+        """Append one frame -- every row of it: the reference's mean runs over all regions, also over those the expansion cuts -- and
+        return its pool id.  A key seen since the last `reset()` returns its id and copies nothing.  An empty frame is an error, as it
+        is for the readers ("Features could not be correctly read")."""
+        known = self._ids.get(key)
+        if known is not None:
+            return known
+        n = int(features.shape[0])
+        if n < 1:
+            raise ValueError(f"ytvln.batch: frame {key!r} is empty: features could not be correctly read")
+        return self._append(key, n, [("features", features), ("geom", geom), ("probs", probs)])
+
+    def expand(self, index: Tensor, boxes: int, view: Optional[Tensor] = None, out=None):
+        """`global_rows` + `expand_records` on the device buffers (a CPU `index` or `view` is uploaded first)."""
+        self._need_device("expand")
+        if torch.is_tensor(index) and not index.is_cuda:
+            index = index.to(self.device, non_blocking=True)
+        if torch.is_tensor(view) and not view.is_cuda:
+            view = view.to(self.device, non_blocking=True)
+        global_rows(self.features, self.offsets, out=self.global_features)
+        return expand_records(self.features, self.geom, self.probs, self.global_features, self.offsets, index, boxes, view=view, out=out,
+                              bad=self.bad)
 
 
 def mask_batch(batch: Sequence[Tensor], vocab_size: int = VOCAB_SIZE, mask_token_id: int = MASK_TOKEN_ID, masked_language: bool = True,

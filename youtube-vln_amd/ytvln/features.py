@@ -10,6 +10,11 @@ feature, whole-image box, uniform class distribution), boxes normalised to [0, 1
 the orientation columns 5-10 (`_get_boxes`, `_get_locations`, `__getitem__`, lines 91-179).  Host-side numpy: this is the loader's
 side of the batch tuple; `ytvln.batch` takes it from there on the device.
 
+    features, geom, probs = reader.records(("123-456", "123-789"))       # PanoFeaturesReader: reader.record("scan-viewpoint")
+
+is the decode-only form for `ytvln.batch.RecordPool`: the stored rows and their raw geometry in fp32, nothing computed; the global
+region, the normalisation and the heading columns are then made on the device (`ytvln.batch.expand_records`).
+
 Backends: a directory path (needs the `lmdb` package -- it is not a dependency of the GPU path and is imported lazily), an object with
 LMDB's `begin()` / `get()` transaction interface, or a plain `dict` mapping key bytes to value bytes (tests, other stores).
 """
@@ -143,9 +148,32 @@ def locations_of(boxes5: np.ndarray) -> np.ndarray:
     return loc
 
 
+def raw_geometry(boxes: np.ndarray, image_width: int, image_height: int, feat_headings=None, feat_elevations=None) -> np.ndarray:
+    """fp32 [n, 8] = x1, y1, x2, y2 in pixels, image width, image height, featureHeading, featureElevation (0 without them): the per-row
+    geometry `ytvln.batch.expand_records` normalises on the device.  Nothing is computed here."""
+    geom = np.zeros((len(boxes), 8), dtype=np.float32)
+    geom[:, :4] = boxes
+    geom[:, 4], geom[:, 5] = image_width, image_height
+    if feat_headings is not None:
+        geom[:, 6], geom[:, 7] = feat_headings, feat_elevations
+    return geom
+
+
 class BaseFeaturesReader(FeaturesReader):
     def _split_key(self, key: str):
         raise NotImplementedError("_split_key: not implemented!")
+
+    def records(self, query: Tuple):
+        """The decode-only counterpart of `__getitem__` for `ytvln.batch.RecordPool`: (features [n, F], geom [n, 8], probs [n, C]), all
+        fp32, the records of the query concatenated as they are stored -- no global region, no mean, no division, no fp64."""
+        l_geom, l_probs, l_features = [], [], []
+        for key, item in zip(list(query), self._items(query)):
+            photo_id, listing_id = self._split_key(key)
+            record = decode_record(item, photo_id, listing_id)
+            l_geom.append(raw_geometry(record.boxes, record.image_width, record.image_height))
+            l_probs.append(record.cls_prob)
+            l_features.append(record.features)
+        return np.concatenate(l_features, axis=0), np.concatenate(l_geom, axis=0), np.concatenate(l_probs, axis=0)
 
     def __getitem__(self, query: Tuple):
         """features_reader.py:153-179."""
@@ -221,12 +249,23 @@ class PanoFeaturesReader(FeaturesReader):
             scan_id, viewpoint_id = key.split("-")
             self.viewpoints.setdefault(scan_id, set()).add(viewpoint_id)
 
-    def __getitem__(self, query: Tuple):
-        key, heading, next_heading = query
+    def _item(self, key: str) -> Dict:
         if key not in self.keys:
             raise TypeError(f"invalid key: {key}")
         with self.envs[self.keys[key]].begin(write=False) as txn:
-            item = decode_pano_record(pickle.loads(bytes(txn.get(key.encode()))))
+            return decode_pano_record(pickle.loads(bytes(txn.get(key.encode()))))
+
+    def record(self, key: str):
+        """The decode-only counterpart of `__getitem__` for `ytvln.batch.RecordPool`: (features [n, F], geom [n, 8], probs [n, C]) of one
+        viewpoint, all fp32, featureHeading / featureElevation in columns 6-7 of `geom`.  The headings of the query are not part of it:
+        they are the `view` input of the expansion, so a viewpoint is one pool frame under whatever headings it is seen."""
+        item = self._item(key)
+        geom = raw_geometry(item["boxes"], item["image_w"], item["image_h"], item["featureHeading"], item["featureElevation"])
+        return item["features"], geom, item["cls_prob"]
+
+    def __getitem__(self, query: Tuple):
+        key, heading, next_heading = query
+        item = self._item(key)
         rec = Record(None, None, len(item["boxes"]), item["image_w"], item["image_h"], item["cls_prob"], item["features"], item["boxes"])
         features, probs = item["features"], item["cls_prob"]
         locations = pano_locations(normalise_boxes(rec), item["featureHeading"], item["featureElevation"], heading, next_heading)

@@ -203,6 +203,13 @@ def make_ragged_pool(bs: int, K: int, T: int, frames: int, boxes: int, F: int = 
         logits -= logits.max(-1, keepdims=True)
         pr = np.exp(logits)
         pool.append((f, loc, pr / pr.sum(-1, keepdims=True)))
+    options, tokens = _pool_options(rs, bs, K, T, frames, vocab)
+    return pool, options, tokens, (tokens > 0).astype(np.int64)
+
+
+def _pool_options(rs, bs: int, K: int, T: int, frames: int, vocab: int):
+    """The nested id lists and tokens of make_ragged_pool / make_record_pool (option structure of make_pool)."""
+    per_item = frames + 2 * (frames // 2)
     options = []
     tokens = np.zeros((bs, K, T), np.int64)
     for i in range(bs):
@@ -228,7 +235,47 @@ def make_ragged_pool(bs: int, K: int, T: int, frames: int, boxes: int, F: int = 
             item.append([int(x) for x in row])
             tokens[i, k] = ins[k] if k in (1, 2) else ins[0]
         options.append(item)
-    return pool, options, tokens, (tokens > 0).astype(np.int64)
+    return options, tokens
+
+
+def make_record_pool(bs: int, K: int, T: int, frames: int, boxes: int, F: int = 2048, C: int = 1601, vocab: int = 30522, seed: int = 1234,
+                     viewpoints: int = 0):
+    """The batch of make_ragged_pool as RAW records, the form consumed by ytvln.batch.RecordPool / expand_records: every distinct frame as
+    `reader.records(...)` returns it -- (features [n, F], geom [n, 8], probs [n, C]), all fp32, n drawn from 1 .. boxes + 3, boxes in
+    pixels, every third frame of two or more rows made of two records with different image sizes -- and the same nested option lists.
+
+    `viewpoints` > 0 makes the re-ranking kind of batch instead: the pool is that many panorama viewpoints (featureHeading and
+    featureElevation in columns 6-7 of geom), shared by all options; option k of an item is a beam, a walk of up to `frames` of them, and
+    every slot has its own (heading, next heading): `view` fp64 [bs, K, frames, 2].  Returns (frames_list, options, tokens [bs,K,T],
+    instr_mask [bs,K,T], view or None)."""
+    rs = np.random.RandomState(seed)
+    P = viewpoints if viewpoints > 0 else bs * (frames + 2 * (frames // 2))
+    pool = []
+    for i, n in enumerate(rs.randint(1, boxes + 4, size=P)):
+        f = np.maximum(rs.standard_normal((n, F)).astype(np.float32), 0.0)
+        geom = np.zeros((n, 8), np.float32)
+        cut = n // 2 if (i % 3 == 2 and n >= 2 and viewpoints <= 0) else n           # rows [0, cut) and [cut, n): one record each
+        for a, b in ((0, cut), (cut, n)):
+            w, h = rs.randint(300, 900, size=2)
+            xy = np.sort(rs.uniform(0, 1, (b - a, 2, 2)), axis=-1)
+            geom[a:b, 0], geom[a:b, 2], geom[a:b, 1], geom[a:b, 3] = xy[:, 0, 0] * w, xy[:, 0, 1] * w, xy[:, 1, 0] * h, xy[:, 1, 1] * h
+            geom[a:b, 4], geom[a:b, 5] = w, h
+        if viewpoints > 0:
+            geom[:, 6:8] = rs.uniform(-3.1, 3.1, (n, 2))
+        logits = rs.standard_normal((n, C)).astype(np.float32) * 3.0
+        logits -= logits.max(-1, keepdims=True)
+        pr = np.exp(logits)
+        pool.append((f, geom, (pr / pr.sum(-1, keepdims=True)).astype(np.float32)))
+    if viewpoints <= 0:
+        options, tokens = _pool_options(rs, bs, K, T, frames, vocab)
+        return pool, options, tokens, (tokens > 0).astype(np.int64), None
+    options = [[[int(x) for x in rs.randint(0, P, size=rs.randint(min(4, frames), frames + 1))] for _ in range(K)] for _ in range(bs)]
+    tokens = np.zeros((bs, K, T), np.int64)
+    for i in range(bs):                                        # re-ranking: one instruction per item, K candidate paths
+        n = rs.randint(min(20, T - 2), T - 1)
+        tokens[i, :, 0], tokens[i, :, 1:1 + n], tokens[i, :, 1 + n] = 101, rs.randint(1000, vocab, size=n), 102
+    view = rs.uniform(-np.pi, np.pi, (bs, K, frames, 2))
+    return pool, options, tokens, (tokens > 0).astype(np.int64), view
 
 
 def to_torch(batch: List[np.ndarray], device="cpu"):
