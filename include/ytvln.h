@@ -122,6 +122,25 @@ int ytvln_gemm_f32_sk(const float* A, int64_t lda, int transA, const float* B, i
  * (*whole_tiles = 1) or the stream-K form, on how many workgroups. */
 int ytvln_gemm_sk_plan(int M, int N, int K, int transA, int epilogue, int* use, int* tile_m, int* tile_n, int* whole_tiles,
                        int* workgroups);
+/* Weight gradients over the valid rows only.  dW = dY^T X is contracted over the rows of the batch; where a padded row of dY is exactly
+ * zero (every Linear of the model: DESIGN.md section 4) its products are 0 * x and need not be formed.
+ *   ytvln_live_rows_list: flags[rows] (one byte per row, non-zero = valid) -> idx[rows + 32] (int32) and count[1] (int32), DEVICE memory.
+ *   idx[0 .. count) = the valid rows, ascending; every later entry holds one row that is not valid (rows - 1 when all are valid).  One
+ *   launch, no atomics, no host read.
+ *   ytvln_gemm_f32_live = ytvln_gemm_f32_rowsum (a_rowsum / rowsum_done: both NULL or both set) whose contraction runs over
+ *   live_idx[0 .. 32 * ceil(*live_count / 32)): k-tile t is list entries 32t .. 32t+31, the same rows for both operands; split s of the
+ *   plan chosen for the full K takes ceil(tiles / splits) live tiles (with fewer than 32 live rows per split: ceil(count / splits) rows each,
+ *   as one padded tile, so that a sparse list is summed in short chains over all splits like the unlisted launch sums it), so count = K
+ *   reproduces the unlisted launch bit for bit, and nothing on
+ *   the host depends on the count (capturable; a replay follows the list in memory).  CONTRACT: rows of op(A)^T = A[k, :] that are not
+ *   listed are all zero and B is finite there.  The list is used when transA = 1, transB = 0, K % 32 == 0, the launch takes the native
+ *   LDS-DMA loop on 256x256 or 128x128 tiles with a K-chunk of at most 4096 rows per split, and the run-time option GEMM_LIVE_ROWS is
+ *   non-zero; any other launch ignores it (same sum, by the contract). */
+int ytvln_live_rows_list(const uint8_t* flags, int rows, int* idx, int* count, void* stream);
+int ytvln_gemm_f32_live(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
+                        int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K, int epilogue,
+                        float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum, int* rowsum_done,
+                        const int* live_idx, const int* live_count, void* stream);
 /* Diagnostics: when `buffer` is non-NULL every workgroup of a persistent launch writes 16 s_memrealtime stamps (100 MHz) to
  * buffer[16 * workgroup + i]: 0 start, 1 ticket drawn, 2 first operands in LDS, then (main loop done, epilogue issued) per piece, 15 end.
  * The buffer must hold 16 * 1024 uint64 (a launch has at most 2 workgroups per CU); NULL switches the stamps off (default). */

@@ -49,6 +49,7 @@ enum Option {
     OPT_GEMM_STAGGER,        // bf16 GEMM, launches of >= 3 rounds of 256x256 tiles: half of the first round starts this many percent of a tile's main loop late (0 = off)
     OPT_ATTN_DKV_SPLIT,      // bf16 attention, d = 128: 1 = dK and dV in two passes with two waves per SIMD each, 0 = one pass with one wave per SIMD
     OPT_GEMM_BF16_WIDE,      // 1: bf16 GEMM outputs leave through LDS-transposed 16-byte stores where the epilogue reads no matrix; 0: 2-byte stores
+    OPT_GEMM_LIVE_ROWS,      // 1 (default): fp32 weight-gradient GEMMs handed a row list (ytvln_gemm_f32_live) contract over the listed rows only; 0: the list is ignored
     OPT_COUNT
 };
 int opt(int id);

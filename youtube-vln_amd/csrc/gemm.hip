@@ -145,8 +145,15 @@ __device__ uint32_t g_f32_probe[128];
 #ifndef YT_GEMM_DMA_SPREAD
 #define YT_GEMM_DMA_SPREAD 1
 #endif
-template <int BM, int BN, bool A_KC, bool B_KC, int NW, int KB, int NS, int WPS, bool X3 = false, int WN = 2>
-__global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const GemmArgs g) {
+// LIVE = true (both operands k-major, square 256 / 128 tiles, native instruction): the contraction runs over a device-side row list
+// (GemmLiveArgs).  A 1 KiB LDS-DMA piece of a k-major operand is one k-row (256-wide tile) or two (128-wide), so the row enters the
+// source address only as row * ld: the workgroup copies its split's slice of the list into the LDS behind the operand ring once, and
+// per k-tile every lane reads the NI rows of its pieces from there (ds_read, counted by the compiler with the fragment reads: the
+// hand-counted vmcnt waits see no new vector-memory operation) and forms base + row * ld with one 32 x 32 -> 64-bit multiply-add per
+// piece.  The LDS image, the fragment reads and the matrix instructions are those of the unlisted kernel; an identity list walks the
+// same tiles in the same order (same bits).
+template <int BM, int BN, bool A_KC, bool B_KC, int NW, int KB, int NS, int WPS, bool X3 = false, int WN = 2, bool LIVE = false>
+__global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const std::conditional_t<LIVE, GemmLiveArgs, GemmArgs> g) {
     using TA = DmaTile<BM, A_KC, NW, KB>;
     using TB = DmaTile<BN, B_KC, NW, KB>;
     constexpr int WM = NW / WN;                        // waves along m x WN along n (2, or 8 for the 224-row tile: eight waves of 224x32)
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const GemmArgs g
     constexpr int SA = BM * KB, SB = BN * KB, STAGE = SA + SB;
     constexpr int NPT = TA::NI + TB::NI;               // DMA instructions per wave per k-tile
     constexpr int NG = KB / 8;                         // 4-deep k-groups per half-wave per k-tile
-    __shared__ __attribute__((aligned(16))) float smem[NS * STAGE];    // ONE shared object (see guide: DMA + 2nd object de-pipelines)
+    __shared__ __attribute__((aligned(16))) float smem[NS * STAGE + (LIVE ? LIVE_CAP : 0)];    // ONE shared object (see guide: DMA + 2nd object de-pipelines)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
@@ -164,8 +171,8 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const GemmArgs g
     const int m0 = tc.m * BM, n0 = tc.n * BN;
     const int kbeg = tc.split * g.kchunk;
     const int kend = min(g.Kloop, kbeg + g.kchunk);
-    const int nk = (kend - kbeg) / KB;
-    const bool tail_here = g.ktail && kend == g.Kloop;       // this workgroup's last k-tiles cross K
+    int nk = (kend - kbeg) / KB;
+    const bool tail_here = !LIVE && g.ktail && kend == g.Kloop;       // this workgroup's last k-tiles cross K
 
     const float* pa[TA::NI];
     const float* pb[TB::NI];
@@ -173,7 +180,52 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const GemmArgs g
     for (int i = 0; i < TA::NI; ++i) pa[i] = TA::src(g.A, g.lda, g.mnA, m0, kbeg, wave, lane, i, 0x7fffffff);
 #pragma unroll
     for (int i = 0; i < TB::NI; ++i) pb[i] = TB::src(g.B, g.ldb, g.mnB, n0, kbeg, wave, lane, i, 0x7fffffff);
-    const int64_t sa = TA::step(g.lda), sb = TB::step(g.ldb);
+    const int64_t sa = LIVE ? 0 : TA::step(g.lda), sb = LIVE ? 0 : TB::step(g.ldb);
+
+    // LIVE: this split's share of the live k-tiles -- nt = ceil(count / 32) tiles in all, c = ceil(nt / splits) per split (the rule the host's
+    // kchunk follows for the full K, so count = K gives today's ranges; a split past the end has no tile and writes zeros; fewer than 32 live
+    // rows per split: one padded tile each, see below) -- and its slice of the list in LDS.  set_rows(t): the sources of this wave's pieces for tile t of the slice; rows are clamped into the operand.
+    const int* lrows = nullptr;
+    const char* ca = nullptr;
+    const char* cb = nullptr;
+    if constexpr (LIVE) {
+        static_assert(!A_KC && !B_KC && !X3 && BM == BN && (BM == 256 || BM == 128) && KB == 32 && NS == 2 && YT_GEMM_DMA_SPREAD && TA::NI == TB::NI,
+                      "live-row form: square k-major tiles on the spread-DMA native loop");
+        const int count = min(max(*g.live_count, 0), g.K);
+        const int nt = (count + KB - 1) / KB;
+        const int share = (count + g.splits - 1) / g.splits;          // live rows per split
+        int e0, ne;          // this split's list entries [e0, e0 + ne); the rest of its last k-tile is filled with the list's padding row
+        if (share >= KB) {          // whole k-tiles: ceil(nt / splits) = ceil(share / 32) of them, the rule kchunk follows
+            const int c = (nt + g.splits - 1) / g.splits;          // <= kchunk / 32 <= LIVE_CAP / 32 (host)
+            const int t0 = min(nt, tc.split * c);
+            nk = min(nt, t0 + c) - t0;
+            e0 = t0 * KB; ne = nk * KB;          // (the list pads its own last tile)
+        } else {
+            // fewer live rows than one k-tile per split: every split takes its `share` of them as ONE padded tile.  Packed into whole tiles
+            // they would be one serial chain of 32 products in the first few splits; the unlisted launch adds them as short chains spread
+            // over all splits, and so does this (its rounding error grows with the chain length)
+            e0 = min(count, tc.split * share);
+            ne = min(count, e0 + share) - e0;
+            nk = ne > 0 ? 1 : 0;
+        }
+        int* lw = reinterpret_cast<int*>(smem + NS * STAGE);
+        for (int e = tid; e < nk * KB; e += NW * 64) lw[e] = g.live_idx[e < ne ? e0 + e : count];          // ([count]: the padding row, its A values are zero)
+        __syncthreads();
+        lrows = lw;
+        const int lcol = (lane % (BM / 4)) * 4;               // a lane's 16-byte column is the same in every piece it owns
+        ca = reinterpret_cast<const char*>(g.A + min(m0 + lcol, g.mnA - 4));
+        cb = reinterpret_cast<const char*>(g.B + min(n0 + lcol, g.mnB - 4));
+    }
+    const uint32_t lda4 = (uint32_t)g.lda * 4u, ldb4 = (uint32_t)g.ldb * 4u;          // LIVE: row pitches in bytes (< 2^32: host)
+    auto set_rows = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TA::NI; ++i) {
+            const int kr = ((wave * TA::NI + i) * 64 + lane) / (BM / 4);          // k-row of piece i inside the tile (wave-uniform at 256, lane >> 5 selects at 128)
+            const uint32_t r = min((uint32_t)lrows[t * KB + kr], (uint32_t)(g.K - 1));
+            pa[i] = reinterpret_cast<const float*>(ca + (uint64_t)r * lda4);
+            pb[i] = reinterpret_cast<const float*>(cb + (uint64_t)r * ldb4);
+        }
+    };
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -213,9 +265,13 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const GemmArgs g
         }
     };
 
+    if constexpr (LIVE) {
+        if (nk > 0) { set_rows(0); issue(0, false); }
+    } else {
 #pragma unroll
     for (int t = 0; t < NS - 1; ++t)
         if (t < nk) issue(t, !YT_GEMM_DMA_SPREAD || X3 || t + 1 < nk);          // (SPREAD re-requests the last tile: the pointers never leave the matrix)
+    }
     int st_out = 0;     // ring slot the MFMAs read
 #if YT_GEMM_PROBE
     uint32_t ts = 0;
@@ -255,6 +311,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const GemmArgs g
         // piece p of the incoming tile (A pieces first); past the last tile the same request with a zero pointer step (a slot nobody reads any more):
         // no branch inside the matrix stream
         const int64_t sa_in = kt + NS < nk ? sa : 0, sb_in = kt + NS < nk ? sb : 0;          // (no step past the last tile: the re-request stays inside the matrix)
+        if constexpr (LIVE) set_rows(min(kt + NS - 1, nk - 1));          // the incoming tile's rows (past the last tile: the last one again)
         auto issue_piece = [&](auto pc) __attribute__((always_inline)) {
             constexpr int pidx = decltype(pc)::value;
             if constexpr (pidx < TA::NI) {
@@ -556,7 +613,7 @@ static Plan plan_gemm(int M, int N, int K, int epilogue, bool big_ok = false, bo
 static int plan_splits(int M, int N, int K, int epilogue) { return plan_gemm(M, N, K, epilogue).splits; }
 
 template <int BM, int BN>
-static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s) {
+static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s, const int* live_idx = nullptr, const int* live_count = nullptr) {
     g.tiles_m = (int)cdiv(g.M, BM);
     g.tiles_n = (int)cdiv(g.N, BN);
     g.ntiles = g.tiles_m * g.tiles_n;
@@ -586,6 +643,15 @@ static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s) {
             //    the forward layout, B = nn.Linear weight [N, K], measured 3 % behind and stays on the two-waves-per-SIMD kernel)
             const bool take = sw == 1 || (sw == 2 && g.splits == 1) || (sw == 3 && BN == 256 && !transB);
             if (take && !g.x3 && launch_sw(BM, BN, g, transA, transB, grid.x, s)) return 0;
+        }
+        if constexpr (BM == BN && (BM == 256 || BM == 128)) {          // live-row contraction (the caller checked the launch: gemm_f32_impl)
+            if (live_idx && transA && !transB && !g.x3) {
+                GemmLiveArgs lg;
+                static_cast<GemmArgs&>(lg) = g;
+                lg.live_idx = live_idx; lg.live_count = live_count;
+                hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, false, false, 8, 32, 2, (BM == 256 ? 2 : 4), false, 2, true>), grid, dim3(512), 0, s, lg);
+                return 0;
+            }
         }
         if constexpr (BM == 224 || BM == 160) {     // 8 waves of BM x 32 (K-contiguous A only: plan_gemm)
             dim3 blk(512);
@@ -655,7 +721,7 @@ extern "C" int64_t ytvln_gemm_workspace_elems(int M, int N, int K, int epilogue)
 static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
                          int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K,
                          int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum, int* rowsum_done,
-                         unsigned* sk_ctl, void* stream) {
+                         unsigned* sk_ctl, void* stream, const int* live_idx = nullptr, const int* live_count = nullptr) {
     if (rowsum_done) *rowsum_done = 0;
     YT_REQUIRE(A && B && C, "gemm: null operand");
     YT_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
@@ -721,22 +787,28 @@ static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B
     if (g.splits == 1) g.kchunk = std::max(g.kchunk, g.Kloop);
     if (g.splits == 1 && asum_ok) g.asum = a_rowsum;
     if (rowsum_done) *rowsum_done = g.asum != nullptr;
+    // live-row contraction (GEMM_LIVE_ROWS): both operands k-major on the native LDS-DMA loop, whole 32-row k-tiles, a K-chunk whose list slice
+    // fits the LDS behind the ring, byte pitches below 2^32; the kernels exist for the 256x256 and 128x128 tiles (launch_tile).  Anything else
+    // runs the plain launch: the listed-out rows of A are zero, so the result is the same sum.
+    if (!(live_idx && live_count && opt(OPT_GEMM_LIVE_ROWS) != 0 && g.fast && transA && !transB && !g.x3 && !g.ktail && K % BK == 0 &&
+          g.kchunk <= LIVE_CAP && lda < ((int64_t)1 << 30) && ldb < ((int64_t)1 << 30)))
+        live_idx = live_count = nullptr;
     if (g.splits > 1) {
-        if (plan.tile == 4) launch_tile<256, 256>(g, transA, transB, s);
+        if (plan.tile == 4) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
         else if (plan.tile == 5 && g.fast && !transA && !g.x3) launch_tile<224, 256>(g, transA, transB, s);
         else if (plan.tile == 6 && g.fast && !transA && !g.x3) launch_tile<160, 256>(g, transA, transB, s);
-        else launch_tile<128, 128>(g, transA, transB, s);
+        else launch_tile<128, 128>(g, transA, transB, s, live_idx, live_count);
         const int64_t total = (int64_t)M * N;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 1024), 2048)), dim3(256), 0, s, workspace, C,
                            ldc, bias, M, N, g.splits, beta, (const float*)g.asum_ws, g.asum);
     } else {
         g.splits = 1;
-        if (plan.tile == 4) launch_tile<256, 256>(g, transA, transB, s);
+        if (plan.tile == 4) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
         else if (plan.tile == 5 && g.fast && !transA && !g.x3) launch_tile<224, 256>(g, transA, transB, s);
         else if (plan.tile == 6 && g.fast && !transA && !g.x3) launch_tile<160, 256>(g, transA, transB, s);
-        else if (plan.tile >= 5) launch_tile<256, 256>(g, transA, transB, s);
+        else if (plan.tile >= 5) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
         else if (plan.tile == 3) launch_tile<256, 128>(g, transA, transB, s);
-        else if (plan.tile == 0) launch_tile<128, 128>(g, transA, transB, s);
+        else if (plan.tile == 0) launch_tile<128, 128>(g, transA, transB, s, live_idx, live_count);
         else if (plan.tile == 1) launch_tile<128, 64>(g, transA, transB, s);
         else launch_tile<64, 64>(g, transA, transB, s);
     }
@@ -767,6 +839,16 @@ extern "C" int ytvln_gemm_f32_sk(const float* A, int64_t lda, int transA, const 
     YT_REQUIRE((a_rowsum == nullptr) == (rowsum_done == nullptr), "gemm_f32_sk: a_rowsum and rowsum_done go together");
     return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
                          a_rowsum, rowsum_done, sk_ctl, stream);
+}
+
+extern "C" int ytvln_gemm_f32_live(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
+                                   int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K,
+                                   int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum,
+                                   int* rowsum_done, const int* live_idx, const int* live_count, void* stream) {
+    YT_REQUIRE((a_rowsum == nullptr) == (rowsum_done == nullptr), "gemm_f32_live: a_rowsum and rowsum_done go together");
+    YT_REQUIRE(live_idx && live_count, "gemm_f32_live: null row list");
+    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
+                         a_rowsum, rowsum_done, nullptr, stream, live_idx, live_count);
 }
 
 extern "C" int ytvln_gemm_sk_plan(int M, int N, int K, int transA, int epilogue, int* use, int* tile_m, int* tile_n, int* whole_tiles,

@@ -32,6 +32,17 @@ struct GemmArgs {
     int split_map;        // 1: split-K workgroups are laid out split-major per XCD (see decode_tile)
 };
 
+// Live-row contraction (gemm_dma_kernel<..., LIVE = true>: weight gradients dW = dY^T X whose padded rows of dY are exact zeros).  The launch
+// contracts over live_idx[0 .. 32 * ceil(*live_count / 32)) instead of 0 .. K-1: k-tile t = list entries 32t .. 32t+31, the same rows for
+// both operands.  Both pointers are DEVICE memory (csrc/live_rows.hip writes them): nothing on the host depends on the count, so the
+// launch is capturable and a replay follows the list of the batch it runs on.  Only the LIVE instantiations take this record; every other
+// kernel keeps GemmArgs as its argument, byte for byte.
+struct GemmLiveArgs : GemmArgs {
+    const int* live_idx;      // [K + 32]: the live rows in ascending order, then (up to the next multiple of 32) a row of A that is all zero
+    const int* live_count;    // [1]
+};
+constexpr int LIVE_CAP = 4096;      // list entries a workgroup keeps in LDS behind its operand ring = the longest K-chunk (per split) a listed launch may have
+
 constexpr int BK = 32;
 
 // Workgroup id -> (tile row, tile column, split).  MI355X dispatches workgroup b to XCD b % 8 and every XCD has its own L2:

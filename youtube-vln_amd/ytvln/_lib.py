@@ -42,6 +42,9 @@ SIGNATURES = {
     "ytvln_gemm_sk_ctl_elems": [],
     "ytvln_gemm_f32_sk": [P, I64, I32, P, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, I32, P, P, P, P],
     "ytvln_gemm_sk_plan": [I32, I32, I32, I32, I32, P, P, P, P, P],
+    # weight gradients over the valid rows only (csrc/live_rows.hip, gemm_dma_kernel<..., LIVE>)
+    "ytvln_live_rows_list": [P, I32, P, P, P],
+    "ytvln_gemm_f32_live": [P, I64, I32, P, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, I32, P, P, P, P, P],
     "ytvln_gemm_probe": [P],
     "ytvln_gemm_bf16_probe": [P, I32, I32],
     "ytvln_colsum_f32": [P, I64, I32, I32, P, I64, I32, P],

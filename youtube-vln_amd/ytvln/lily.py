@@ -30,6 +30,8 @@ class Lily(PreTrainedModel):
         if self.args.model_name != "vilbert":
             raise NotImplementedError(f"model_name={self.args.model_name!r}: only 'vilbert' exists in the reference factories")
         self.bert = BERT_MODEL_FACTORY[self.args.model_name](config)
+        # the pre-training losses read no padded row (ignore index / target masks): weight gradients contract over the valid rows only
+        self.bert.wgrad_live_rows = True
         self.cls = CLS_MODEL_FACTORY[self.args.model_name](config, self.bert.embeddings.word_embeddings.weight)
         bi_hidden_size = config.bi_hidden_size
         self.vil_logit = torch.nn.Linear(bi_hidden_size, 1)
@@ -53,7 +55,7 @@ class Lily(PreTrainedModel):
         if head_rows:
             rows = {k: head_rows[n] for k, n in (("t", "language"), ("v", "vision")) if n in head_rows}
         linguistic_prediction, vision_prediction, _ = self.cls(sequence_output_t, sequence_output_v, pooled_output_t,
-                                                               pooled_output_v, heads=want, rows=rows)
+                                                               pooled_output_v, heads=want, rows=rows, live=self.bert.live_rows)
 
         if self.fusion_method == "sum":
             pooled_output = pooled_output_t + pooled_output_v

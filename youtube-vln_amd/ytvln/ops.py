@@ -307,10 +307,11 @@ def _bf16_eligible(M: int, N: int, K: int) -> bool:
     return _MATMUL_PRECISION == "bf16" and M >= 64 and N >= 64 and K >= 64
 
 
-def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, ldaux=0, epi=EPI_NONE, beta=0.0, flags=0, rowsum=None):
+def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, ldaux=0, epi=EPI_NONE, beta=0.0, flags=0, rowsum=None, live=None):
     """fp32 operands (native fp32 matrix instruction, or the three-bf16-term form under "fp32x3").  `rowsum` = an [M] tensor that should
     receive sum_k op(A)[m, k] (the bias gradient riding on a weight-gradient GEMM, ytvln_gemm_f32_rowsum); returns True when the launch
-    produced it, False when the caller has to run `colsum` itself."""
+    produced it, False when the caller has to run `colsum` itself.  `live` = the LiveRows of the K rows a weight-gradient launch (transA = 1)
+    contracts over: rows of A outside the list are exact zeros (ytvln_gemm_f32_live)."""
     sk = _lib.option("GEMM_SK") != 0          # the persistent kernel (opt-in): its partial-tile scratch and control block exist only then
     key = (M, N, K, epi, sk)
     need = _WS_CACHE.get(key)
@@ -320,6 +321,12 @@ def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, 
     if _MATMUL_PRECISION == "fp32x3":
         flags = int(flags) | GEMM_SPLIT_BF16X3
     ctl = _sk_ctl(C.device) if sk else None
+    if live is not None and transA and not transB and live.rows == K and _MATMUL_PRECISION == "fp32":
+        done = ctypes.c_int(0)
+        call("ytvln_gemm_f32_live", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
+             M, N, K, epi, float(beta), _ptr(ws), need, int(flags), _ptr(rowsum), ctypes.byref(done) if rowsum is not None else None,
+             live.idx.data_ptr(), live.count.data_ptr(), _stream())
+        return bool(done.value)
     if rowsum is not None:
         done = ctypes.c_int(0)
         call("ytvln_gemm_f32_sk", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
@@ -328,6 +335,65 @@ def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, 
     call("ytvln_gemm_f32_sk", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
          M, N, K, epi, float(beta), _ptr(ws), need, int(flags), None, None, _ptr(ctl), _stream())
     return False
+
+
+class LiveRows:
+    """ytvln_live_rows_list's outputs for one padding mask: `idx` [rows + 32] int32 (the valid rows, ascending, then one padded row repeated),
+    `count` [1] int32 -- device tensors -- and the host integer `rows`."""
+    __slots__ = ("idx", "count", "rows")
+
+    def __init__(self, idx, count, rows):
+        self.idx, self.count, self.rows = idx, count, int(rows)
+
+    def record_stream(self, stream) -> None:
+        self.idx.record_stream(stream)
+        self.count.record_stream(stream)
+
+
+def live_rows(mask: Tensor) -> LiveRows:
+    """List of the rows of `mask` (any shape; non-zero = valid).  One launch, no host sync."""
+    if not mask.is_cuda:
+        raise RuntimeError(f"ytvln.ops: `mask` must live on the GPU (no CPU fallback); got device {mask.device}")
+    rows = mask.numel()
+    flags = (mask.reshape(-1) != 0).contiguous()          # one byte per row
+    idx = torch.empty(rows + 32, dtype=torch.int32, device=mask.device)
+    count = torch.empty(1, dtype=torch.int32, device=mask.device)
+    call("ytvln_live_rows_list", flags.data_ptr(), rows, idx.data_ptr(), count.data_ptr(), _stream())
+    return LiveRows(idx, count, rows)
+
+
+_LIVE_SCOPE = None          # the LiveRows of the side of the model whose projections are being called (BertModel sets it per side), or None
+live_rows_probe = None      # tests: callable(dy [M, N], LiveRows), called by every backward that hands a list to its weight-gradient launch
+
+
+@contextlib.contextmanager
+def live_rows_scope(live: Optional[LiveRows]):
+    """Projections called inside (LinearFn, FFNFn, ImageEmbedFn) contract their weight gradients over `live`: the caller's promise that the
+    gradient of every such projection's output is exactly zero on the rows that are not listed."""
+    global _LIVE_SCOPE
+    prev, _LIVE_SCOPE = _LIVE_SCOPE, live
+    try:
+        yield
+    finally:
+        _LIVE_SCOPE = prev
+
+
+def _live_for(M: int, fmt) -> Optional[LiveRows]:
+    """The list a forward keeps for its backward: fp32 rows, and the rows of the call are the rows of the scope.  (Callers ask only when an
+    input needs a gradient; inside an autograd Function's forward the grad mode itself is always off.)"""
+    live = _LIVE_SCOPE
+    if live is None or fmt is not _F32 or live.rows != M or _MATMUL_PRECISION != "fp32":
+        return None
+    return live
+
+
+def _live_kw(live: Optional[LiveRows], dy: Tensor) -> dict:
+    """Keywords of a weight-gradient launch (none without a list: the bf16 GEMM keeps its signature)."""
+    if live is None:
+        return {}
+    if live_rows_probe is not None:
+        live_rows_probe(dy, live)
+    return {"live": live}
 
 
 _SK_CTL = {}
@@ -687,6 +753,7 @@ class LinearFn(torch.autograd.Function):
             z = fmt.empty(M, N, dev) if (epi == EPI_GELU and need_grad) else None
             fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
         ctx.epi, ctx.dims, ctx.lda, ctx.has_bias = epi, (M, N, K), lda, bias is not None
+        ctx.live = _live_for(M, fmt) if need_grad else None
         ctx.in_shape = x.shape
         ctx.targets = _targets_of(weight)
         ctx.btargets = _targets_of(bias) if bias is not None else None
@@ -739,7 +806,7 @@ class LinearFn(torch.autograd.Function):
             if dw is None:
                 dw = torch.empty((N, K), dtype=torch.float32, device=dev)
             # dW[N, K] = dY^T X; db = column sums of dY = row sums of the A operand (dY^T) of this launch: rides on the GEMM when it can
-            db_done = fmt.gemm(dy, ldy, 1, x2, ctx.lda, 0, dw, K, N, K, M, flags=flags, rowsum=db if want_db else None)
+            db_done = fmt.gemm(dy, ldy, 1, x2, ctx.lda, 0, dw, K, N, K, M, flags=flags, rowsum=db if want_db else None, **_live_kw(ctx.live, dy))
         if want_db and not db_done:
             d32, ld32 = fmt.f32_rows(dy, ldy, N)
             colsum(d32, M, N, ld32, out=db)
@@ -789,6 +856,7 @@ class FFNFn(torch.autograd.Function):
         y = fmt.empty(M, N, dev)
         fmt.gemm(h, I, 0, *fmt.weight(w2), 1, y, N, M, N, I, bias=b2)
         ctx.dims, ctx.lda, ctx.in_shape = (M, K, I, N), lda, x.shape
+        ctx.live = _live_for(M, fmt) if need_grad else None
         ctx.targets = (_targets_of(w1), _targets_of(w2), _targets_of(b1), _targets_of(b2))
         ctx.save_for_backward(x2, w1, w2, z, None if ctx.recompute_h else h)
         out = y.view(*x.shape[:-1], N)
@@ -819,7 +887,7 @@ class FFNFn(torch.autograd.Function):
         if h is None:          # recompute_h: h = gelu(z), alive for the one GEMM that reads it
             h = fmt.empty(M, I, dev)
             call("ytvln_gelu_fwd_f32", _ptr(z), _ptr(h), M * I, _stream())
-        db2_done = fmt.gemm(dy, ldy, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2)          # db2 rides on the dW2 GEMM
+        db2_done = fmt.gemm(dy, ldy, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2, **_live_kw(ctx.live, dy))          # db2 rides on the dW2 GEMM
         del h
         if not db2_done:
             d32, ld32 = fmt.f32_rows(dy, ldy, N)
@@ -840,7 +908,7 @@ class FFNFn(torch.autograd.Function):
         dw1 = _direct_grad(ctx.targets[0], (I, K))
         if dw1 is None:
             dw1 = torch.empty((I, K), dtype=torch.float32, device=dev)
-        if not fmt.gemm(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1):
+        if not fmt.gemm(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1, **_live_kw(ctx.live, dz)):
             d32, ld32 = fmt.f32_rows(dz, I, I)
             colsum(d32, M, I, ld32, out=db1)
         return (dx, dw1, db1, dw2, db2) + tail
@@ -1136,6 +1204,7 @@ class ImageEmbedFn(torch.autograd.Function):
              _ptr(ws[3]), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(s), _ptr(mean), _ptr(rstd), rows, H, float(eps), float(p_post),
              _ptr(rng) if rng is not None else None, int(site), _stream())
         ctx.meta = (rows, H, p_post, site, E.shape[0])
+        ctx.live = _live_for(rows, _F32 if not bf16 else None) if need_grad else None
         ctx.save_for_backward(locc, s, mean, rstd, gamma, rng)
         return y
 
@@ -1149,7 +1218,7 @@ class ImageEmbedFn(torch.autograd.Function):
         dimg, _, ds, dg, db = _ln_bwd(dy, s, mean, rstd, gamma, rows, H, 0.0, p_post, rng, site, fmt=_format_of(s), want_f32=True)
         dev = ds.device
         dwall = torch.empty((H, 12), dtype=torch.float32, device=dev)
-        _gemm(ds, H, 1, locc, 12, 0, dwall, 12, H, 12, rows)               # ds^T . loc  -> [H, 12]
+        _gemm(ds, H, 1, locc, 12, 0, dwall, 12, H, 12, rows, **_live_kw(ctx.live, ds))               # ds^T . loc  -> [H, 12]
         dbias = colsum(ds, rows, H, H)
         dE = colsum_by_index(ds, rows, H, H, KT, idx_f32=locc, idx_stride=12, idx_f32_offset=11)
         return (dimg.view(dy.shape), None, dwall[:, 0:5].contiguous(), dbias, dwall[:, 5:9].contiguous(), dbias,

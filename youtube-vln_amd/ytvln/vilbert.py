@@ -108,6 +108,14 @@ class _Runtime:
     ffn_recompute: bool = False          # BertEncoder.recompute == "ffn", for the duration of that encoder's forward (read by _ffn_block)
     plans = None                         # BertModel.skip_padding: (text RowsPlan | None, image RowsPlan | None) while such a forward, or the
                                          # recomputation of one of its layers, runs; None = every row of both streams is padded (the default)
+    live = None                          # (text LiveRows | None, image LiveRows | None) while a training forward of BertModel with padding masks runs
+
+
+def _live(side: int):
+    """Context for the projections of the text (0) / image (1) side: their weight gradients contract over that side's valid rows
+    (ops.live_rows_scope) while BertModel has lists installed, a plain pass-through otherwise."""
+    live = _Runtime.live
+    return contextlib.nullcontext() if live is None or live[side] is None else ops.live_rows_scope(live[side])
 
 
 def _plan(side: int):
@@ -612,11 +620,12 @@ class BertBiAttention(nn.Module):
         m1, m2 = _mask2d(attention_mask1, n, r), _mask2d(attention_mask2, n, t)
         # each stream's input feeds two projections and the residual of BertBiOutput: the residual value travels through both
         # projections' autograd nodes (ops.LinearFn passthrough) so the three gradients meet inside the input-gradient GEMMs
-        q1, res1 = ops.linear_res(input_tensor1, self.query1.weight, self.query1.bias)
-        kv1, res1 = ops.linear_res(res1, ops.pack_rows(self.key1.weight, self.value1.weight), ops.pack_rows(self.key1.bias, self.value1.bias))
+        with _live(1):
+            q1, res1 = ops.linear_res(input_tensor1, self.query1.weight, self.query1.bias)
+            kv1, res1 = ops.linear_res(res1, ops.pack_rows(self.key1.weight, self.value1.weight), ops.pack_rows(self.key1.bias, self.value1.bias))
         if plan_v is not None:
             q1, kv1 = ops.rows_unpack(q1.view(-1, hb), plan_v), ops.rows_unpack(kv1.view(-1, 2 * hb), plan_v)
-        with ops.TwoStream.side(input_tensor2):         # the text side's projections: second HIP stream when two-stream mode is on
+        with ops.TwoStream.side(input_tensor2), _live(0):         # the text side's projections: second HIP stream when two-stream mode is on
             q2, res2 = ops.linear_res(input_tensor2, self.query2.weight, self.query2.bias)
             kv2, res2 = ops.linear_res(res2, ops.pack_rows(self.key2.weight, self.value2.weight), ops.pack_rows(self.key2.bias, self.value2.bias))
             if plan_t is not None:
@@ -659,8 +668,9 @@ class BertBiOutput(nn.Module):
         self.q_dropout2 = nn.Dropout(config.hidden_dropout_prob)
 
     def forward(self, hidden_states1, input_tensor1, hidden_states2, input_tensor2):
-        c1 = ops.linear(hidden_states1, self.dense1.weight, self.dense1.bias)
-        with ops.TwoStream.side(hidden_states2, input_tensor2):
+        with _live(1):
+            c1 = ops.linear(hidden_states1, self.dense1.weight, self.dense1.bias)
+        with ops.TwoStream.side(hidden_states2, input_tensor2), _live(0):
             c2 = ops.linear(hidden_states2, self.dense2.weight, self.dense2.bias)
         h1 = _add_ln(self.LayerNorm1, c1, input_tensor1, self, p_pre=self.dropout1.p)
         with ops.TwoStream.side():
@@ -684,8 +694,9 @@ class BertConnectionLayer(nn.Module):
             input_tensor1, attention_mask1, input_tensor2, attention_mask2, co_attention_mask, use_co_attention_mask)
         # bi_output2 (image queries over text) feeds the vision stream, bi_output1 the text stream (vilbert.py:671)
         attention_output1, attention_output2 = self.biOutput(bi_output2, res1, bi_output1, res2)
-        layer_output1 = _ffn_block(self.v_intermediate, self.v_output, attention_output1)
-        with ops.TwoStream.side():
+        with _live(1):
+            layer_output1 = _ffn_block(self.v_intermediate, self.v_output, attention_output1)
+        with ops.TwoStream.side(), _live(0):
             layer_output2 = _ffn_block(self.t_intermediate, self.t_output, attention_output2)
         return layer_output1, layer_output2, co_attention_probs
 
@@ -803,8 +814,9 @@ class BertEncoder(nn.Module):
 
         for count, (v_end, t_end) in enumerate(zip(self.v_biattention_id, self.t_biattention_id)):
             assert self.fixed_t_layer <= t_end and self.fixed_v_layer <= v_end
-            image_embedding = run(self.v_layer, v_start, v_end, image_embedding, image_attention_mask, att_v, self.fixed_v_layer, "v")
-            with ts.side(txt_embedding, txt_attention_mask):
+            with _live(1):
+                image_embedding = run(self.v_layer, v_start, v_end, image_embedding, image_attention_mask, att_v, self.fixed_v_layer, "v")
+            with ts.side(txt_embedding, txt_attention_mask), _live(0):
                 txt_embedding = run(self.layer, t_start, t_end, txt_embedding, txt_attention_mask, att_t, self.fixed_t_layer, "t")
             if count == 0 and self.in_batch_pairs:
                 # every text of the batch against every image of the batch: B -> B^2 rows (vilbert.py:771-778); row (i, j) = text i, image j
@@ -842,8 +854,9 @@ class BertEncoder(nn.Module):
             if output_all_encoded_layers:
                 all_t.append(txt_embedding)
                 all_v.append(image_embedding)
-        image_embedding = run(self.v_layer, v_start, len(self.v_layer), image_embedding, image_attention_mask, att_v, 0, "v")
-        with ts.side(txt_embedding, txt_attention_mask):
+        with _live(1):
+            image_embedding = run(self.v_layer, v_start, len(self.v_layer), image_embedding, image_attention_mask, att_v, 0, "v")
+        with ts.side(txt_embedding, txt_attention_mask), _live(0):
             txt_embedding = run(self.layer, t_start, len(self.layer), txt_embedding, txt_attention_mask, att_t, 0, "t")
         ts.end(txt_embedding, *all_t, *(p for p in att_t if p is not None))
         if not output_all_encoded_layers:
@@ -947,11 +960,15 @@ class BertPreTrainingHeads(nn.Module):
         self.fusion_method = config.fusion_method
         self.dropout = nn.Dropout(0.1)
 
-    def forward(self, sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, heads=("t", "v", "rel"), rows=None):
+    def forward(self, sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, heads=("t", "v", "rel"), rows=None, live=None):
         """Returns (prediction_scores_t, prediction_scores_v, seq_relationship_score) like vilbert.py:939-954.
         `heads` lets a caller that discards a head (Lily, lily.py:87) skip its GEMMs; skipped entries are None.
         `rows` = {"t": idx, "v": idx} (optional) decodes only the listed rows of the flattened [N*T, H] / [N*R, Hv] sequences
-        (loss-aware heads: the scores come back as [len(idx), vocab] instead of [N, T, vocab])."""
+        (loss-aware heads: the scores come back as [len(idx), vocab] instead of [N, T, vocab]).
+        `live` = BertModel.live_rows of the forward that produced the sequences: the transforms' and decoders' weight gradients contract over
+        the valid rows (a head that decodes gathered `rows` keeps the plain launch)."""
+        live_t = None if live is None or (rows is not None and "t" in rows) else live[0]
+        live_v = None if live is None or (rows is not None and "v" in rows) else live[1]
         if rows is not None:
             if "t" in rows:
                 sequence_output_t = ops.gather_rows(sequence_output_t.reshape(-1, sequence_output_t.shape[-1]), rows["t"])
@@ -963,12 +980,14 @@ class BertPreTrainingHeads(nn.Module):
             pooled = pooled_output_t * pooled_output_v
         else:
             assert False
-        scores_t = self.predictions(sequence_output_t) if "t" in heads else None
+        with ops.live_rows_scope(live_t):
+            scores_t = self.predictions(sequence_output_t) if "t" in heads else None
         rel = None
         if "rel" in heads:
             pooled = ops.dropout(pooled, self.dropout.p, self.training, _drop_state(self, pooled))
             rel = ops.linear(pooled, self.bi_seq_relationship.weight, self.bi_seq_relationship.bias)
-        scores_v = self.imagePredictions(sequence_output_v) if "v" in heads else None
+        with ops.live_rows_scope(live_v):
+            scores_v = self.imagePredictions(sequence_output_v) if "v" in heads else None
         return scores_t, scores_v, rel
 
 
@@ -1064,6 +1083,7 @@ class BertModel(BertPreTrainedModel):
             self.encoder.recompute = args.recompute
         if args is not None and hasattr(args, "skip_padding"):
             self.skip_padding = args.skip_padding
+        self.live_rows = None                 # (text LiveRows | None, image LiveRows | None) of the last forward when it built them, for the prediction heads
         self.padding_overflow = None          # device int64 [2] (text, image) once a skip_padding forward has run: valid rows that did not fit, summed
 
     # Extension, opt-in (a plain attribute like encoder.recompute; taken from config.args.skip_padding when that field exists): padding-free
@@ -1078,6 +1098,13 @@ class BertModel(BertPreTrainedModel):
     # additive mask (their softmax weight is exactly 0) and no loss reads them, so losses and gradients are those of the padded run at p = 0.
     # With dropout on, the LayerNorm / FFN / image-embedding sites hash packed coordinates: other masks of the same distribution.
     skip_padding = None
+
+    # Weight gradients over the valid rows only (run-time option GEMM_LIVE_ROWS).  The gradient of every projection's output
+    # is exactly zero on a padded row -- padded rows are keys behind the -10000 mask (exp gives exactly 0), the poolers read row 0, LayerNorm /
+    # GELU' / dropout backward map a zero row to a zero row -- PROVIDED no loss reads a padded row of the sequence outputs.  That holds for the
+    # pre-training losses (ignore_index / target masks), so the pre-training model (Lily) switches it on for its encoder; a bare BertModel and
+    # the models that hand per-row outputs to arbitrary losses (VILBertForVLTasks) keep the plain launches.
+    wgrad_live_rows = False
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
                 co_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
@@ -1107,10 +1134,23 @@ class BertModel(BertPreTrainedModel):
 
         ts = ops.TwoStream
         plan_t, plan_v = self._plans(attention_mask, image_attention_mask)          # (None, None) unless skip_padding is set
+        # weight gradients over the valid rows only: one list per padding mask, built here and read by the backward of every projection of that
+        # side.  Training with gradients on and padded rows only (packed rows need no list; the pair geometries re-batch one side's rows)
+        self.live_rows = None
+        if (self.wgrad_live_rows and self.training and torch.is_grad_enabled() and plan_t is None and plan_v is None and ops.get_matmul_precision() == "fp32"
+                and not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE) and ops._lib.option("GEMM_LIVE_ROWS") != 0):
+            lists = tuple(None if m is None or m.numel() % 32 != 0 else ops.live_rows(m) for m in (attention_mask, image_attention_mask))
+            if lists[0] is not None or lists[1] is not None:
+                self.live_rows = lists
         try:
+            _Runtime.live = self.live_rows
             if not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE):
                 ts.begin(input_imgs.device)              # two-stream mode: the text side starts at its embeddings
                 _share_drop_state()
+                if ts.active and self.live_rows is not None:          # made on the main stream, read by the text side's backward launches
+                    for lr in self.live_rows:
+                        if lr is not None:
+                            lr.record_stream(ts.side_stream(input_imgs.device))
                 if ts.active and plan_t is not None:          # made on the main stream in front of the fork, read by the text side's launches
                     plan_t.record_stream(ts.side_stream(input_imgs.device))
             with ts.side(input_txt, token_type_ids, ext_t):
@@ -1120,7 +1160,8 @@ class BertModel(BertPreTrainedModel):
             if plan_v is not None:          # the 2048-wide feature projection and the fused embedding run on packed rows (bf16 mode: packed, then cast)
                 input_imgs = ops.rows_pack(input_imgs if input_imgs.dtype == torch.float32 else input_imgs.float(), plan_v).unsqueeze(0)
                 image_loc = ops.rows_pack(image_loc if image_loc.dtype == torch.float32 else image_loc.float(), plan_v).unsqueeze(0)
-            v_embedding_output = self.v_embeddings(input_imgs, image_loc)
+            with _live(1):
+                v_embedding_output = self.v_embeddings(input_imgs, image_loc)
             _Runtime.plans = (plan_t, plan_v) if (plan_t is not None or plan_v is not None) else None
             encoded_layers_t, encoded_layers_v, all_attention_mask = self.encoder(
                 embedding_output, v_embedding_output, ext_t, ext_v, ext_co,
@@ -1128,6 +1169,7 @@ class BertModel(BertPreTrainedModel):
         finally:
             ts.active = False
             _Runtime.plans = None
+            _Runtime.live = None
         if plan_t is not None:          # back to [N, T, H]: padded rows are exact zeros
             encoded_layers_t = [ops.rows_unpack(h.view(plan_t.capacity, -1), plan_t).view(n, t, -1) for h in encoded_layers_t]
         if plan_v is not None:
@@ -1177,7 +1219,7 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
             input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
             output_all_encoded_layers=False, output_all_attention_masks=output_all_attention_masks)
         prediction_scores_t, prediction_scores_v, seq_relationship_score = self.cls(
-            sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v)
+            sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, live=self.bert.live_rows)
         if masked_lm_labels is not None and next_sentence_label is not None and image_target is not None:
             n, r, c = prediction_scores_v.shape
             pv = prediction_scores_v[:, 1:].reshape(n * (r - 1), c)                      # region 0 dropped (:1429)
