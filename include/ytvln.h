@@ -141,6 +141,30 @@ int ytvln_gemm_f32_live(const float* A, int64_t lda, int transA, const float* B,
                         int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K, int epilogue,
                         float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum, int* rowsum_done,
                         const int* live_idx, const int* live_count, void* stream);
+/* Forward and input-gradient projections on the valid rows only (transA = 0: Y = X W^T, dX = dY W).
+ *   ytvln_live_rows_perm: flags[rows] as for ytvln_live_rows_list -> perm[rows] (int32) and count[1] (int32), DEVICE memory: the valid rows
+ *   ascending, then the rows that are not valid ascending -- a permutation of 0 .. rows-1 whose first `count` entries are that call's idx.
+ *   One launch, no atomics, no host read.
+ *   ytvln_gemm_f32_rows = ytvln_gemm_f32 whose M dimension runs over the list: position p stands for row row_perm[p] of A, of C and of aux.
+ *   Positions 0 .. *row_count-1 are computed exactly as the unlisted launch on the same plan computes those rows (an identity list gives its
+ *   bits).  The rows listed behind the count are DEAD: A is not read there, and the launch leaves them defined -- exact zeros in C, and in
+ *   aux where YTVLN_EPI_GELU writes its pre-activation, with beta = 0; untouched with beta != 0.  row_perm must be a permutation of
+ *   0 .. M-1 (entries are clamped into the matrix).  Both pointers are DEVICE memory and the grid covers the full M, so nothing on the host
+ *   depends on the count (capturable).  m_hint (HOST, 0 = M): the number of rows the caller expects to be listed; it replaces M in the
+ *   planner's choice of the tile and nowhere else -- a wrong hint costs time, never rows or bits.  Listed launches take 128x128 tiles (with
+ *   split-K by list position and a list-aware reduce) or 256x256 tiles; the split count is always the unlisted launch's, so the bits of a
+ *   listed row depend neither on the list nor on the hint.  The list is used when transA = 0, fp32 without
+ *   YTVLN_GEMM_SPLIT_BF16X3, K % 32 == 0, the operands meet the LDS-DMA path's alignment, and the run-time option GEMM_LIVE_M is
+ *   non-zero; any other launch ignores it and computes every row, dead ones included (A must then be readable there).
+ *   ytvln_gemm_rows_workspace_elems: workspace for ytvln_gemm_f32_rows at this hint (>= ytvln_gemm_workspace_elems).
+ *   ytvln_gemm_rows_plan (host only): the tile and split count a listed launch of this aligned problem takes. */
+int ytvln_live_rows_perm(const uint8_t* flags, int rows, int* perm, int* count, void* stream);
+int ytvln_gemm_f32_rows(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
+                        int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K, int epilogue,
+                        float beta, float* workspace, int64_t workspace_elems, int flags, const int* row_perm,
+                        const int* row_count, int m_hint, void* stream);
+int64_t ytvln_gemm_rows_workspace_elems(int M, int N, int K, int epilogue, int m_hint);
+int ytvln_gemm_rows_plan(int M, int N, int K, int epilogue, int m_hint, int* tile_m, int* tile_n, int* splits);
 /* Diagnostics: when `buffer` is non-NULL every workgroup of a persistent launch writes 16 s_memrealtime stamps (100 MHz) to
  * buffer[16 * workgroup + i]: 0 start, 1 ticket drawn, 2 first operands in LDS, then (main loop done, epilogue issued) per piece, 15 end.
  * The buffer must hold 16 * 1024 uint64 (a launch has at most 2 workgroups per CU); NULL switches the stamps off (default). */

@@ -50,6 +50,7 @@ enum Option {
     OPT_ATTN_DKV_SPLIT,      // bf16 attention, d = 128: 1 = dK and dV in two passes with two waves per SIMD each, 0 = one pass with one wave per SIMD
     OPT_GEMM_BF16_WIDE,      // 1: bf16 GEMM outputs leave through LDS-transposed 16-byte stores where the epilogue reads no matrix; 0: 2-byte stores
     OPT_GEMM_LIVE_ROWS,      // 1 (default): fp32 weight-gradient GEMMs handed a row list (ytvln_gemm_f32_live) contract over the listed rows only; 0: the list is ignored
+    OPT_GEMM_LIVE_M,         // 1 (default): fp32 forward / input-gradient GEMMs handed a row list (ytvln_gemm_f32_rows) compute the listed rows only; 0: the list is ignored
     OPT_COUNT
 };
 int opt(int id);
@@ -164,7 +165,10 @@ __device__ __forceinline__ float gelu_erf(float x) { return x * 0.5f * (1.0f + e
 __device__ __forceinline__ float dgelu_erf(float x) {
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
     const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
-    return cdf + x * pdf;
+    // (written as ONE fused multiply-add: `cdf + x * pdf` is a sum of two products, 0.5 * (..) and x * pdf, and the compiler may fuse either
+    //  one into the add -- it chose differently between two inlined copies of this function, and a row-listed GEMM epilogue must give the bits
+    //  of the unlisted one)
+    return fmaf(x, pdf, cdf);
 }
 
 // The same two functions for the bf16-RESIDENT path, whose every result is rounded to bf16 (8 significant bits) on its way out: Phi(x) by

@@ -152,8 +152,15 @@ __device__ uint32_t g_f32_probe[128];
 // hand-counted vmcnt waits see no new vector-memory operation) and forms base + row * ld with one 32 x 32 -> 64-bit multiply-add per
 // piece.  The LDS image, the fragment reads and the matrix instructions are those of the unlisted kernel; an identity list walks the
 // same tiles in the same order (same bits).
-template <int BM, int BN, bool A_KC, bool B_KC, int NW, int KB, int NS, int WPS, bool X3 = false, int WN = 2, bool LIVE = false>
-__global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const std::conditional_t<LIVE, GemmLiveArgs, GemmArgs> g) {
+//
+// ROWS = true (K-contiguous A, native instruction, any tile of the WN-wide wave grids): the M dimension runs over a device-side row list
+// (GemmRowsArgs).  Tile position p stands for row row_perm[p] of A, C and aux; only the first *row_count positions are computed.  The row
+// enters the A source pointers once, in the prologue; main loop, LDS image and fragment reads are the unlisted kernel's.  The grid covers
+// the full M: workgroups are renumbered so that the tiles holding live positions come first and spread over all XCDs (the plain map would
+// hand the dead half of the tile range to half of the XCDs), and a workgroup whose tile lies wholly behind the count skips loads and matrix
+// work and only defines the dead rows (epilogue_rows_body; split-K: nothing -- the list-aware reduce writes them).
+template <int BM, int BN, bool A_KC, bool B_KC, int NW, int KB, int NS, int WPS, bool X3 = false, int WN = 2, bool LIVE = false, bool ROWS = false>
+__global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const std::conditional_t<LIVE, GemmLiveArgs, std::conditional_t<ROWS, GemmRowsArgs, GemmArgs>> g) {
     using TA = DmaTile<BM, A_KC, NW, KB>;
     using TB = DmaTile<BN, B_KC, NW, KB>;
     constexpr int WM = NW / WN;                        // waves along m x WN along n (2, or 8 for the 224-row tile: eight waves of 224x32)
@@ -162,22 +169,63 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const std::condi
     constexpr int SA = BM * KB, SB = BN * KB, STAGE = SA + SB;
     constexpr int NPT = TA::NI + TB::NI;               // DMA instructions per wave per k-tile
     constexpr int NG = KB / 8;                         // 4-deep k-groups per half-wave per k-tile
-    __shared__ __attribute__((aligned(16))) float smem[NS * STAGE + (LIVE ? LIVE_CAP : 0)];    // ONE shared object (see guide: DMA + 2nd object de-pipelines)
+    static_assert(!ROWS || (A_KC && !X3 && !LIVE && BM % 4 == 0), "row-listed form: K-contiguous A on the native loop");
+    __shared__ __attribute__((aligned(16))) float smem[NS * STAGE + (LIVE ? LIVE_CAP : ROWS ? BM : 0)];    // ONE shared object (see guide: DMA + 2nd object de-pipelines)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
     const int wm0 = (wave / WN) * (BM / WM), wn0 = (wave % WN) * (BN / WN);
-    const TileCoord tc = decode_tile(blockIdx.x, g.tiles_m, g.tiles_n, g.splits, g.split_map);
+    TileCoord tc;
+    int rcount = 0;          // ROWS: positions to compute
+    if constexpr (ROWS) {
+        rcount = min(max(*g.row_count, 0), g.M);
+        const int lm = (rcount + BM - 1) / BM, nl = lm * g.tiles_n, nlw = nl * g.splits;          // tile rows / tiles / workgroups with live positions
+        const int bid = blockIdx.x;
+        if (bid < nlw) {          // live tiles first, split-major and grouped inside each XCD's share like decode_tile
+            const int id = xcd_remap(bid, nlw);
+            const int split = id / nl;
+            tc = tile_coord(id - split * nl, lm, g.tiles_n);
+            tc.split = split;
+        } else {
+            if (g.splits > 1) return;          // (the whole workgroup: rows_reduce_kernel defines the dead rows of a split-K launch)
+            const int id = bid - nlw;
+            tc.m = lm + id / g.tiles_n; tc.n = id % g.tiles_n; tc.split = 0;
+        }
+    } else {
+        tc = decode_tile(blockIdx.x, g.tiles_m, g.tiles_n, g.splits, g.split_map);
+    }
     const int m0 = tc.m * BM, n0 = tc.n * BN;
     const int kbeg = tc.split * g.kchunk;
     const int kend = min(g.Kloop, kbeg + g.kchunk);
     int nk = (kend - kbeg) / KB;
-    const bool tail_here = !LIVE && g.ktail && kend == g.Kloop;       // this workgroup's last k-tiles cross K
+    const bool tail_here = !LIVE && !ROWS && g.ktail && kend == g.Kloop;       // this workgroup's last k-tiles cross K
+    // ROWS: the tile's list entries behind the operand ring -- the row of every position, flagged where it is dead or past M -- for the A sources
+    // below and for the epilogue.  (Rows are clamped into the matrix: a damaged list must not steer a store outside C.)
+    const int* lrow = nullptr;
+    if constexpr (ROWS) {
+        int* lw = reinterpret_cast<int*>(smem + NS * STAGE);
+        for (int e = tid; e < BM; e += NW * 64) {
+            const int p = m0 + e;
+            lw[e] = p < g.M ? ((int)min((uint32_t)g.row_perm[p], (uint32_t)(g.M - 1)) | (p < rcount ? 0 : ROW_DEAD)) : ROW_NONE;
+        }
+        __syncthreads();
+        lrow = lw;
+        if (m0 >= rcount) nk = 0;          // nothing to compute: the epilogue writes the zeros
+    }
 
     const float* pa[TA::NI];
     const float* pb[TB::NI];
 #pragma unroll
-    for (int i = 0; i < TA::NI; ++i) pa[i] = TA::src(g.A, g.lda, g.mnA, m0, kbeg, wave, lane, i, 0x7fffffff);
+    for (int i = 0; i < TA::NI; ++i) {
+        if constexpr (ROWS) {          // TA::src with the row looked up: positions behind the tile's last live one repeat it (never stored)
+            const int m = (wave * TA::NI + i) * TA::RP + lane / TA::GR;
+            const int last = max(min(BM, rcount - m0), 1) - 1;
+            const int row = lrow[min(m, last)] & 0x7fffffff;
+            pa[i] = g.A + (int64_t)row * g.lda + kbeg + 4 * ((lane % TA::GR) ^ TA::swz(m));
+        } else {
+            pa[i] = TA::src(g.A, g.lda, g.mnA, m0, kbeg, wave, lane, i, 0x7fffffff);
+        }
+    }
 #pragma unroll
     for (int i = 0; i < TB::NI; ++i) pb[i] = TB::src(g.B, g.ldb, g.mnB, n0, kbeg, wave, lane, i, 0x7fffffff);
     const int64_t sa = LIVE ? 0 : TA::step(g.lda), sb = LIVE ? 0 : TB::step(g.ldb);
@@ -449,7 +497,12 @@ __global__ __launch_bounds__(NW * 64, WPS) void gemm_dma_kernel(const std::condi
 #if YT_GEMM_DMA_SPREAD
     if (!X3) wait_vmcnt<0>();          // the trailing (repeated) requests have landed before this workgroup's LDS is handed on
 #endif
-    gemm_epilogue<TM, TN>(g, acc, m0 + wm0, n0 + wn0, l31, half, tc.split);
+    if constexpr (ROWS) {
+        if (g.splits > 1) epilogue_partials<TM, TN>(g, acc, m0 + wm0, n0 + wn0, l31, half, tc.split);          // by POSITION: rows_reduce_kernel maps them
+        else gemm_epilogue_rows<TM, TN>(g, acc, lrow + wm0, n0 + wn0, l31, half);
+    } else {
+        gemm_epilogue<TM, TN>(g, acc, m0 + wm0, n0 + wn0, l31, half, tc.split);
+    }
 }
 
 // The three-term (X3) kernels are instantiated in their own translation unit -- gemm_x3.hip includes this file with YT_GEMM_X3_TU
@@ -524,6 +577,35 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
                 *cp = acc;
             }
         }
+    }
+}
+
+// The reduce of a row-listed split-K launch (GemmRowsArgs): the partials lie by list POSITION, ws[s][p][:]; position p < count goes to row
+// perm[p] of C in the same fixed split order (+ bias, + beta * C), a position behind the count names a dead row: zeros with beta = 0, untouched
+// otherwise.  Its partials are never read (the workgroups of a wholly dead tile write none).  N % 4 == 0, ldc % 4 == 0 and a 16-byte aligned C: the launch checks them (gemm_f32_impl) and stays unlisted otherwise.
+__global__ __launch_bounds__(256) void rows_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C, int64_t ldc, const float* __restrict__ bias,
+                                                          int M, int N, int splits, float beta, const int* __restrict__ perm,
+                                                          const int* __restrict__ count) {
+    const int n4 = N >> 2;
+    const int live = min(max(*count, 0), M);
+    const int64_t total = (int64_t)M * N, groups = (int64_t)M * n4;
+    for (int64_t gidx = (int64_t)blockIdx.x * 256 + threadIdx.x; gidx < groups; gidx += (int64_t)gridDim.x * 256) {
+        const int p = (int)(gidx / n4), col = (int)(gidx % n4) << 2;
+        const int row = (int)min((uint32_t)perm[p], (uint32_t)(M - 1));
+        float4* cp = reinterpret_cast<float4*>(C + (int64_t)row * ldc + col);
+        if (p >= live) {
+            if (beta == 0.f) *cp = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const int64_t i = (int64_t)p * N + col;
+        float4 acc = *reinterpret_cast<const float4*>(ws + i);
+        for (int s = 1; s < splits; ++s) {
+            const float4 v = *reinterpret_cast<const float4*>(ws + (int64_t)s * total + i);
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+        if (bias) { acc.x += bias[col]; acc.y += bias[col + 1]; acc.z += bias[col + 2]; acc.w += bias[col + 3]; }
+        if (beta != 0.f) { const float4 o = *cp; acc.x += beta * o.x; acc.y += beta * o.y; acc.z += beta * o.z; acc.w += beta * o.w; }
+        *cp = acc;
     }
 }
 
@@ -678,6 +760,37 @@ static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s, const
     return 0;
 }
 
+// Row-listed launches (gemm_dma_kernel<..., ROWS>) exist for the 128x128 tile, with or without split-K, and for the 256x256 tile: the two forms
+// the planner takes once half of M is gone (a launch that filled one round of 256- / 224- / 160-row tiles at the full M fills one or two rounds
+// of 128x128 at the live rows).  The 224- / 160-row tiles, the 4-wave tiles and the one-wave-per-SIMD form are not instantiated.
+template <int BM, int BN>
+static void launch_rows_tile(GemmArgs& g, int transB, hipStream_t s, const int* perm, const int* count) {
+    g.tiles_m = (int)cdiv(g.M, BM);          // the grid covers the full M: the count is device data
+    g.tiles_n = (int)cdiv(g.N, BN);
+    g.ntiles = g.tiles_m * g.tiles_n;
+    GemmRowsArgs rg;
+    static_cast<GemmArgs&>(rg) = g;
+    rg.row_perm = perm; rg.row_count = count;
+    constexpr int WPS = BM == 256 ? 2 : 4;
+    const dim3 grid(g.ntiles * g.splits), blk(512);
+    if (transB) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, true, true, 8, 32, 2, WPS, false, 2, false, true>), grid, blk, 0, s, rg);
+    else hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, true, false, 8, 32, 2, WPS, false, 2, false, true>), grid, blk, 0, s, rg);
+}
+
+// The plan of a listed launch.  The SPLIT COUNT is the unlisted launch's, whatever the hint: the bits of a row depend on the plan only through
+// the split count (every tile walks the same 32-deep k-tiles in the same order), so a listed row carries the bits of the unlisted launch, and
+// a step gives the same bits whether its hint was absent, stale or exact (tests/test_bf16_host_gpu.py runs the same step three times and
+// wants every gradient bit-identical; the hint arrives between the first and the second).  m_hint (0 = M) replaces M in the choice of the
+// tile: 256x256 where it is cheaper for that many rows and the launch does not split, else 128x128.
+static Plan plan_rows(int M, int N, int K, int epilogue, int m_hint) {
+    Plan p = {0, plan_gemm(M, N, K, epilogue, true, false, false).splits};
+    const int Mh = m_hint > 0 ? std::min(m_hint, M) : M;
+    const int force_tile = opt(OPT_GEMM_TILE);
+    if (p.splits == 1 && Mh >= 256 && force_tile != 0 &&
+        (force_tile == 4 || plan_cost(Mh, N, K, 4, 1, epilogue) < 0.995 * plan_cost(Mh, N, K, 0, 1, epilogue)))
+        p.tile = 4;
+    return p;
+}
 
 }  // namespace ytvln
 
@@ -721,7 +834,8 @@ extern "C" int64_t ytvln_gemm_workspace_elems(int M, int N, int K, int epilogue)
 static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
                          int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K,
                          int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum, int* rowsum_done,
-                         unsigned* sk_ctl, void* stream, const int* live_idx = nullptr, const int* live_count = nullptr) {
+                         unsigned* sk_ctl, void* stream, const int* live_idx = nullptr, const int* live_count = nullptr,
+                         const int* row_perm = nullptr, const int* row_count = nullptr, int m_hint = 0) {
     if (rowsum_done) *rowsum_done = 0;
     YT_REQUIRE(A && B && C, "gemm: null operand");
     YT_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
@@ -752,6 +866,36 @@ static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B
     if (!ma_ok && apad && transA && lda >= m4 && M >= 4) { ma_ok = true; g.mnA = m4; }
     g.fast = (K > 0) && k_ok && g.vecA && g.vecB && ma_ok && (!transB ? (N % 4 == 0 && N >= 4) : true) &&
              !opt(OPT_GEMM_GENERIC);
+    // row-listed launch (GEMM_LIVE_M): K-contiguous A on the native LDS-DMA loop, whole k-tiles.  The tile is chosen for m_hint rows (0 = M) among
+    // those that exist in this form, the split count is the unlisted launch's (plan_rows); the grid still covers M, so a wrong hint costs time and
+    // never rows.  Anything else runs the plain launch:
+    // every row is computed and the list is ignored (next to the live-row test further down: the two forms never meet, transA differs).
+    // The opt-in forms (persistent kernel, one-wave-per-SIMD kernel) and a GEMM_TILE forced to a tile that has no listed form launch what they
+    // launch today.
+    const int ftile = opt(OPT_GEMM_TILE);
+    const bool rows_form = row_perm && row_count && opt(OPT_GEMM_LIVE_M) != 0 && g.fast && !transA && !g.x3 && !g.ktail && K % BK == 0 && !a_rowsum &&
+                           opt(OPT_GEMM_SK) == 0 && opt(OPT_GEMM_SW) == 0 && (ftile < 0 || ftile == 0 || ftile == 4);
+    const Plan rplan = rows_form ? plan_rows(M, N, K, epilogue, m_hint) : Plan{0, 1};
+    // split-K: partials by list position, reduced by rows_reduce_kernel in 16-byte pieces of a row -- N % 4 == 0 (B = [N, K] may have any N),
+    // aligned rows of C, and the workspace.  A split launch without them stays unlisted rather than change its split count.
+    const bool red_ok = N % 4 == 0 && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && workspace &&
+                        workspace_elems >= (int64_t)rplan.splits * M * N;
+    if (rows_form && (rplan.splits == 1 || red_ok)) {
+        const Plan plan = rplan;
+        if (plan.splits > 1) {
+            g.kchunk = (int)cdiv(cdiv(K, plan.splits), BK) * BK;
+            g.splits = (int)cdiv(K, g.kchunk);
+            g.ws = workspace;
+        }
+        if (g.splits == 1) g.kchunk = std::max(g.kchunk, g.Kloop);
+        if (plan.tile == 4) launch_rows_tile<256, 256>(g, transB, s, row_perm, row_count);
+        else launch_rows_tile<128, 128>(g, transB, s, row_perm, row_count);
+        if (g.splits > 1)
+            hipLaunchKernelGGL(rows_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)M * N, 1024), 2048)), dim3(256), 0, s, workspace, C, ldc,
+                               bias, M, N, g.splits, beta, row_perm, row_count);
+        YT_LAUNCH_CHECK("gemm_f32 (row list)");
+        return 0;
+    }
     // the 256-row tiles take either A layout: K-contiguous (forward / input gradients) and M-contiguous (weight gradients; 256x256 + split-K
     // competes with 128x128 since round 2), in the native and in the three-term form
     const bool ta_native = g.fast && transA && !g.x3;
@@ -849,6 +993,32 @@ extern "C" int ytvln_gemm_f32_live(const float* A, int64_t lda, int transA, cons
     YT_REQUIRE(live_idx && live_count, "gemm_f32_live: null row list");
     return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
                          a_rowsum, rowsum_done, nullptr, stream, live_idx, live_count);
+}
+
+extern "C" int ytvln_gemm_f32_rows(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
+                                   int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K,
+                                   int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags,
+                                   const int* row_perm, const int* row_count, int m_hint, void* stream) {
+    YT_REQUIRE(row_perm && row_count, "gemm_f32_rows: null row list");
+    YT_REQUIRE(m_hint >= 0, "gemm_f32_rows: negative m_hint %d", m_hint);
+    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
+                         nullptr, nullptr, nullptr, stream, nullptr, nullptr, row_perm, row_count, m_hint);
+}
+
+extern "C" int64_t ytvln_gemm_rows_workspace_elems(int M, int N, int K, int epilogue, int m_hint) {
+    int64_t need = ytvln_gemm_workspace_elems(M, N, K, epilogue);          // (the launch may fall back to the unlisted plan)
+    if (M > 0 && N > 0 && K > 0) {
+        const int splits = plan_rows(M, N, K, epilogue, m_hint).splits;
+        if (splits > 1) need = std::max<int64_t>(need, (int64_t)splits * M * N);
+    }
+    return need;
+}
+
+extern "C" int ytvln_gemm_rows_plan(int M, int N, int K, int epilogue, int m_hint, int* tile_m, int* tile_n, int* splits) {
+    YT_REQUIRE(tile_m && tile_n && splits && M > 0 && N > 0 && K > 0 && m_hint >= 0, "gemm_rows_plan: bad argument");
+    const Plan p = plan_rows(M, N, K, epilogue, m_hint);
+    *tile_m = *tile_n = p.tile == 4 ? 256 : 128; *splits = p.splits;
+    return 0;
 }
 
 extern "C" int ytvln_gemm_sk_plan(int M, int N, int K, int transA, int epilogue, int* use, int* tile_m, int* tile_n, int* whole_tiles,

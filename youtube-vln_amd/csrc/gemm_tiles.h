@@ -43,6 +43,19 @@ struct GemmLiveArgs : GemmArgs {
 };
 constexpr int LIVE_CAP = 4096;      // list entries a workgroup keeps in LDS behind its operand ring = the longest K-chunk (per split) a listed launch may have
 
+// Row-listed output (gemm_dma_kernel<..., ROWS = true>: forward and input-gradient GEMMs of a padded batch, K-contiguous A).  Position p of
+// row_perm is row row_perm[p] of A, of C and of aux.  row_perm is a permutation of 0 .. M-1 (csrc/live_rows.hip: the valid rows ascending,
+// then the padded rows ascending) and only its first *row_count positions are computed; the positions behind them name the DEAD rows, which
+// the launch leaves defined: exact zeros in C (and in aux where the GELU epilogue writes it) with beta = 0, untouched with beta != 0.
+// Both pointers are DEVICE memory and the grid is sized for the full M, so nothing on the host depends on the count.
+struct GemmRowsArgs : GemmArgs {
+    const int* row_perm;      // [M]
+    const int* row_count;     // [1]
+};
+// what a ROWS workgroup keeps per tile position in the LDS behind its operand ring
+constexpr int ROW_DEAD = (int)0x80000000;      // flag on a row that is listed behind the count
+constexpr int ROW_NONE = -1;                   // position past M
+
 constexpr int BK = 32;
 
 // Workgroup id -> (tile row, tile column, split).  MI355X dispatches workgroup b to XCD b % 8 and every XCD has its own L2:
@@ -268,13 +281,11 @@ __device__ __forceinline__ void epilogue_interior(const GemmArgs& g, f32x16 (&ac
     });
 }
 
-// HAND = false: interior tiles that READ a matrix (beta, x GELU', x ReLU') take epilogue_body's compiler-counted loads instead of the
-// hand-counted ones of epilogue_interior.  For kernels that are allowed a scratch segment (_build.py SCRATCH_OK): a register the allocator
-// spills or copies between a hand-issued load and its hand-counted wait is read before the data lands (ADVICE r5).
-template <int TM, int TN, bool HAND = true>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[TM][TN], int row0, int col0, int l31, int half, int split) {
+// raw partial sums of a split-K launch; bias / beta are applied by splitk_reduce_kernel in a fixed order
+template <int TM, int TN>
+__device__ __forceinline__ void epilogue_partials(const GemmArgs& g, f32x16 (&acc)[TM][TN], int row0, int col0, int l31, int half, int split) {
     const bool interior = row0 + 32 * TM <= g.M && col0 + 32 * TN <= g.N;
-    if (g.splits > 1) {      // raw partial sums; bias / beta are applied by splitk_reduce_kernel in a fixed order
+    {
         float* w = g.ws + (int64_t)split * g.M * g.N;
         if (interior) {          // scalar row bases + one per-lane offset (see epilogue_interior)
             const uint32_t vw = (uint32_t)(((int64_t)(4 * half) * g.N + l31) * 4);
@@ -308,8 +319,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[T
                 }
             }
         }
-        return;
     }
+}
+
+// HAND = false: interior tiles that READ a matrix (beta, x GELU', x ReLU') take epilogue_body's compiler-counted loads instead of the
+// hand-counted ones of epilogue_interior.  For kernels that are allowed a scratch segment (_build.py SCRATCH_OK): a register the allocator
+// spills or copies between a hand-issued load and its hand-counted wait is read before the data lands (ADVICE r5).
+template <int TM, int TN, bool HAND = true>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[TM][TN], int row0, int col0, int l31, int half, int split) {
+    const bool interior = row0 + 32 * TM <= g.M && col0 + 32 * TN <= g.N;
+    if (g.splits > 1) { epilogue_partials<TM, TN>(g, acc, row0, col0, l31, half, split); return; }
 #define YT_EPI(E)                                                                        \
     case E:                                                                              \
         if (interior) {                                                                  \
@@ -331,6 +350,72 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[T
             break;
     }
 #undef YT_EPI
+}
+
+// Epilogue of a row-listed tile (GemmRowsArgs).  lrow = the wave's slice of the tile's list entries in LDS: the row of A / C / aux behind each
+// tile position, flagged ROW_DEAD when the position lies behind the count and ROW_NONE when it lies past M.  The two half-waves of a store hold
+// different rows, so there is no scalar row base: every access is column base + row * ld per lane, counted by the compiler (no hand-issued
+// loads: nothing here depends on the register allocator).  The arithmetic is epilogue_body's, term for term -- the same bits on a listed row.
+// A dead row is written as zeros (beta = 0: C, and aux where GELU writes its pre-activation) or left alone (beta != 0).
+template <int TM, int TN, int EPI>
+__device__ __forceinline__ void epilogue_rows_body(const GemmArgs& g, f32x16 (&acc)[TM][TN], const int* lrow, int col0, int l31, int half) {
+    constexpr bool AUX_IN = EPI == YTVLN_EPI_MUL_DGELU || EPI == YTVLN_EPI_MUL_DRELU;
+    const bool has_beta = g.beta != 0.f;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int col = col0 + 32 * j + l31;
+        if (col >= g.N) continue;
+        const float bv = g.bias ? g.bias[col] : 0.f;
+        float* const cc = g.C + col;
+        float* const xc = (EPI != YTVLN_EPI_NONE && EPI != YTVLN_EPI_RELU && g.aux) ? g.aux + col : nullptr;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {          // 4 rows (8q + 4 half + 0..3) at a time, like epilogue_body
+                const int4 e4 = *reinterpret_cast<const int4*>(lrow + 32 * i + 8 * q + 4 * half);
+                const int e[4] = {e4.x, e4.y, e4.z, e4.w};
+                float ax[4], old[4];
+                if (AUX_IN) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) ax[u] = e[u] >= 0 ? xc[(int64_t)e[u] * g.ldaux] : 0.f;
+                }
+                if (has_beta) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) old[u] = e[u] >= 0 ? cc[(int64_t)e[u] * g.ldc] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool dead = e[u] < 0;
+                    if (e[u] == ROW_NONE || (dead && has_beta)) continue;
+                    const int64_t row = e[u] & 0x7fffffff;
+                    float v = acc[i][j][4 * q + u] + bv;
+                    if (EPI == YTVLN_EPI_GELU) {
+                        if (xc) xc[row * g.ldaux] = dead ? 0.f : v;
+                        v = gelu_erf(v);
+                    } else if (EPI == YTVLN_EPI_RELU) {
+                        v = fmaxf(v, 0.f);
+                    } else if (EPI == YTVLN_EPI_MUL_DGELU) {
+                        v *= dgelu_erf(ax[u]);
+                    } else if (EPI == YTVLN_EPI_MUL_DRELU) {
+                        v = ax[u] > 0.f ? v : 0.f;
+                    }
+                    if (has_beta) v += g.beta * old[u];
+                    cc[row * g.ldc] = dead ? 0.f : v;
+                }
+            }
+        }
+    }
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void gemm_epilogue_rows(const GemmArgs& g, f32x16 (&acc)[TM][TN], const int* lrow, int col0, int l31, int half) {
+    switch (g.epilogue) {
+        case YTVLN_EPI_GELU: epilogue_rows_body<TM, TN, YTVLN_EPI_GELU>(g, acc, lrow, col0, l31, half); break;
+        case YTVLN_EPI_RELU: epilogue_rows_body<TM, TN, YTVLN_EPI_RELU>(g, acc, lrow, col0, l31, half); break;
+        case YTVLN_EPI_MUL_DGELU: epilogue_rows_body<TM, TN, YTVLN_EPI_MUL_DGELU>(g, acc, lrow, col0, l31, half); break;
+        case YTVLN_EPI_MUL_DRELU: epilogue_rows_body<TM, TN, YTVLN_EPI_MUL_DRELU>(g, acc, lrow, col0, l31, half); break;
+        default: epilogue_rows_body<TM, TN, YTVLN_EPI_NONE>(g, acc, lrow, col0, l31, half); break;
+    }
 }
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;

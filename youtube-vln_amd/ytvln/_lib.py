@@ -45,6 +45,11 @@ SIGNATURES = {
     # weight gradients over the valid rows only (csrc/live_rows.hip, gemm_dma_kernel<..., LIVE>)
     "ytvln_live_rows_list": [P, I32, P, P, P],
     "ytvln_gemm_f32_live": [P, I64, I32, P, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, I32, P, P, P, P, P],
+    # forward / input-gradient GEMMs over the valid rows only (gemm_dma_kernel<..., ROWS>)
+    "ytvln_live_rows_perm": [P, I32, P, P, P],
+    "ytvln_gemm_f32_rows": [P, I64, I32, P, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, I32, P, P, I32, P],
+    "ytvln_gemm_rows_workspace_elems": [I32, I32, I32, I32, I32],
+    "ytvln_gemm_rows_plan": [I32, I32, I32, I32, I32, P, P, P],
     "ytvln_gemm_probe": [P],
     "ytvln_gemm_bf16_probe": [P, I32, I32],
     "ytvln_colsum_f32": [P, I64, I32, I32, P, I64, I32, P],
@@ -167,7 +172,7 @@ SIGNATURES = {
     "ytvln_rccl_async_error": [P],
     "ytvln_rccl_destroy": [P],
 }
-RESTYPES = {"ytvln_weight_norm_workspace_elems": I64, "ytvln_row_logit_workspace_elems": I64, "ytvln_attn_problem_size": I64, "ytvln_attn_bwd_workspace_elems": I64, "ytvln_attn_dbias_workspace_elems": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
+RESTYPES = {"ytvln_weight_norm_workspace_elems": I64, "ytvln_row_logit_workspace_elems": I64, "ytvln_attn_problem_size": I64, "ytvln_attn_bwd_workspace_elems": I64, "ytvln_attn_dbias_workspace_elems": I64, "ytvln_attn_bias_size": I64, "ytvln_gemm_workspace_elems": I64, "ytvln_gemm_rows_workspace_elems": I64, "ytvln_attn_keep_bytes": I64, "ytvln_gemm_sk_ctl_elems": I64, "ytvln_gemm_bf16_workspace_elems": I64, "ytvln_rccl_library_path": C.c_char_p, "ytvln_option_name": C.c_char_p}
 DT_F32, DT_F64, DT_BF16, DT_I64, DT_U8 = 0, 1, 2, 3, 4
 RED_SUM, RED_MAX, RED_MIN = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128

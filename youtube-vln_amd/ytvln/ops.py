@@ -307,12 +307,25 @@ def _bf16_eligible(M: int, N: int, K: int) -> bool:
     return _MATMUL_PRECISION == "bf16" and M >= 64 and N >= 64 and K >= 64
 
 
-def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, ldaux=0, epi=EPI_NONE, beta=0.0, flags=0, rowsum=None, live=None):
+def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, ldaux=0, epi=EPI_NONE, beta=0.0, flags=0, rowsum=None, live=None,
+          rows=None):
     """fp32 operands (native fp32 matrix instruction, or the three-bf16-term form under "fp32x3").  `rowsum` = an [M] tensor that should
     receive sum_k op(A)[m, k] (the bias gradient riding on a weight-gradient GEMM, ytvln_gemm_f32_rowsum); returns True when the launch
     produced it, False when the caller has to run `colsum` itself.  `live` = the LiveRows of the K rows a weight-gradient launch (transA = 1)
-    contracts over: rows of A outside the list are exact zeros (ytvln_gemm_f32_live)."""
+    contracts over: rows of A outside the list are exact zeros (ytvln_gemm_f32_live).  `rows` = the LiveRows (with `perm`) of the M rows a
+    forward / input-gradient launch (transA = 0) computes: the rows behind the count come back as zeros (beta = 0) or untouched
+    (ytvln_gemm_f32_rows); a hint equal to M means "every row is expected to be listed" and launches the plain form."""
     sk = _lib.option("GEMM_SK") != 0          # the persistent kernel (opt-in): its partial-tile scratch and control block exist only then
+    if (rows is not None and rows.perm is not None and not transA and rows.rows == M and rows.hint < M and rowsum is None
+            and _MATMUL_PRECISION == "fp32"):
+        key = (M, N, K, epi, sk, "rows", rows.hint)
+        need = _WS_CACHE.get(key)
+        if need is None:
+            need = _WS_CACHE[key] = int(_lib.load().ytvln_gemm_rows_workspace_elems(M, N, K, epi, rows.hint))
+        ws = torch.empty(need, dtype=torch.float32, device=C.device) if need else None
+        call("ytvln_gemm_f32_rows", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
+             M, N, K, epi, float(beta), _ptr(ws), need, int(flags), rows.perm.data_ptr(), rows.count.data_ptr(), rows.hint, _stream())
+        return False
     key = (M, N, K, epi, sk)
     need = _WS_CACHE.get(key)
     if need is None:
@@ -339,19 +352,25 @@ def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, 
 
 class LiveRows:
     """ytvln_live_rows_list's outputs for one padding mask: `idx` [rows + 32] int32 (the valid rows, ascending, then one padded row repeated),
-    `count` [1] int32 -- device tensors -- and the host integer `rows`."""
-    __slots__ = ("idx", "count", "rows")
+    `count` [1] int32 -- device tensors -- and the host integer `rows`.  With `perm` [rows] int32 (ytvln_live_rows_perm: the valid rows, then
+    the padded rows, both ascending) the input-gradient GEMMs of the scope compute the listed rows only -- dY is zero on the others, so nothing
+    observable changes -- and, with `forward` set, the forward GEMMs too: the padded rows of every projection's output are then ZEROS, which
+    reaches the padded rows of the model's own outputs (BertModel.forward_live_rows).  `hint` is the HOST's guess of the count for the launch
+    plans (0 = none yet; equal to `rows` = expect no padding: plain launches)."""
+    __slots__ = ("idx", "count", "rows", "perm", "hint", "forward")
 
-    def __init__(self, idx, count, rows):
-        self.idx, self.count, self.rows = idx, count, int(rows)
+    def __init__(self, idx, count, rows, perm=None, hint=0, forward=False):
+        self.idx, self.count, self.rows, self.perm, self.hint, self.forward = idx, count, int(rows), perm, int(hint), bool(forward)
 
     def record_stream(self, stream) -> None:
         self.idx.record_stream(stream)
         self.count.record_stream(stream)
+        if self.perm is not None:
+            self.perm.record_stream(stream)
 
 
-def live_rows(mask: Tensor) -> LiveRows:
-    """List of the rows of `mask` (any shape; non-zero = valid).  One launch, no host sync."""
+def live_rows(mask: Tensor, perm: bool = False) -> LiveRows:
+    """List of the rows of `mask` (any shape; non-zero = valid).  One launch, no host sync; `perm` = one more for the permutation."""
     if not mask.is_cuda:
         raise RuntimeError(f"ytvln.ops: `mask` must live on the GPU (no CPU fallback); got device {mask.device}")
     rows = mask.numel()
@@ -359,7 +378,11 @@ def live_rows(mask: Tensor) -> LiveRows:
     idx = torch.empty(rows + 32, dtype=torch.int32, device=mask.device)
     count = torch.empty(1, dtype=torch.int32, device=mask.device)
     call("ytvln_live_rows_list", flags.data_ptr(), rows, idx.data_ptr(), count.data_ptr(), _stream())
-    return LiveRows(idx, count, rows)
+    pm = None
+    if perm:
+        pm = torch.empty(rows, dtype=torch.int32, device=mask.device)
+        call("ytvln_live_rows_perm", flags.data_ptr(), rows, pm.data_ptr(), count.data_ptr(), _stream())          # (the same count again)
+    return LiveRows(idx, count, rows, pm)
 
 
 _LIVE_SCOPE = None          # the LiveRows of the side of the model whose projections are being called (BertModel sets it per side), or None
@@ -369,7 +392,9 @@ live_rows_probe = None      # tests: callable(dy [M, N], LiveRows), called by ev
 @contextlib.contextmanager
 def live_rows_scope(live: Optional[LiveRows]):
     """Projections called inside (LinearFn, FFNFn, ImageEmbedFn) contract their weight gradients over `live`: the caller's promise that the
-    gradient of every such projection's output is exactly zero on the rows that are not listed."""
+    gradient of every such projection's output is exactly zero on the rows that are not listed.  Where the list carries `perm` their
+    input-gradient GEMMs compute the listed rows only (same promise), and where it also has `forward` set their forward GEMMs do: the second
+    promise is then that nothing reads the other rows of their outputs as data (a padded row is a key behind the -10000 mask)."""
     global _LIVE_SCOPE
     prev, _LIVE_SCOPE = _LIVE_SCOPE, live
     try:
@@ -394,6 +419,11 @@ def _live_kw(live: Optional[LiveRows], dy: Tensor) -> dict:
     if live_rows_probe is not None:
         live_rows_probe(dy, live)
     return {"live": live}
+
+
+def _rows_kw(live: Optional[LiveRows], forward: bool = False) -> dict:
+    """Keywords of an input-gradient (or, `forward`, a forward) launch with transA = 0 inside the scope: the rows it may leave out."""
+    return {} if live is None or live.perm is None or (forward and not live.forward) else {"rows": live}
 
 
 _SK_CTL = {}
@@ -738,9 +768,10 @@ class LinearFn(torch.autograd.Function):
         need_grad = any(ctx.needs_input_grad)
         epi = _ACT[act]
         dev = x.device
+        live = _live_for(M, fmt)          # inside a live_rows_scope with `forward` set: the GEMM computes the valid rows, padded rows of y (and z) are zeros
         if epi == ACT_SWISH:          # unfused: the plain GEMM writes the pre-activation z (kept for the backward), then y = z * sigmoid(z)
             z, ldy = fmt.empty(M, N, dev), N
-            fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, z, N, M, N, K, bias=bias)
+            fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, z, N, M, N, K, bias=bias, **_rows_kw(live, True))
             y = torch.empty_like(z) if need_grad else z          # nothing to keep without a backward: in place
             call("ytvln_act_fwd_" + fmt.suffix, _ptr(z), _ptr(y), M * N, ACT_SWISH, _stream())
             if out is not fmt:
@@ -751,9 +782,9 @@ class LinearFn(torch.autograd.Function):
             else:          # (an fp32 activation output stays dense: the ReLU backward reads it as its aux)
                 y, ldy = out.empty(M, N, dev), N
             z = fmt.empty(M, N, dev) if (epi == EPI_GELU and need_grad) else None
-            fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi)
+            fmt.gemm(x2, lda, 0, *fmt.weight(weight), 1, y, ldy, M, N, K, bias=bias, aux=z, ldaux=N, epi=epi, **_rows_kw(live, True))
         ctx.epi, ctx.dims, ctx.lda, ctx.has_bias = epi, (M, N, K), lda, bias is not None
-        ctx.live = _live_for(M, fmt) if need_grad else None
+        ctx.live = live if need_grad else None
         ctx.in_shape = x.shape
         ctx.targets = _targets_of(weight)
         ctx.btargets = _targets_of(bias) if bias is not None else None
@@ -791,11 +822,11 @@ class LinearFn(torch.autograd.Function):
             w, ldw = fmt.weight(weight)
             acc = fmt.accumulate_target(dres, M, K, dy, dy_in)
             if acc is not None:          # dx = d(residual) + dY W, written over the residual branch's gradient
-                fmt.gemm(dy, ldy, 0, w, ldw, 0, acc, K, M, K, N, beta=1.0, flags=flags)
+                fmt.gemm(dy, ldy, 0, w, ldw, 0, acc, K, M, K, N, beta=1.0, flags=flags, **_rows_kw(ctx.live))
                 dx = acc.view(ctx.in_shape)
             else:
                 dx = fmt.empty(M, K, dev)
-                fmt.gemm(dy, ldy, 0, w, ldw, 0, dx, K, M, K, N, flags=flags)
+                fmt.gemm(dy, ldy, 0, w, ldw, 0, dx, K, M, K, N, flags=flags, **_rows_kw(ctx.live))
                 dx = dx.view(ctx.in_shape)
                 if dres is not None:
                     dx = dx + dres.reshape(ctx.in_shape)
@@ -852,11 +883,12 @@ class FFNFn(torch.autograd.Function):
         dev = x.device
         h = fmt.empty(M, I, dev)
         z = fmt.empty(M, I, dev) if need_grad else None
-        fmt.gemm(x2, lda, 0, *fmt.weight(w1), 1, h, I, M, I, K, bias=b1, aux=z, ldaux=I, epi=EPI_GELU)
+        live = _live_for(M, fmt)
+        fmt.gemm(x2, lda, 0, *fmt.weight(w1), 1, h, I, M, I, K, bias=b1, aux=z, ldaux=I, epi=EPI_GELU, **_rows_kw(live, True))
         y = fmt.empty(M, N, dev)
-        fmt.gemm(h, I, 0, *fmt.weight(w2), 1, y, N, M, N, I, bias=b2)
+        fmt.gemm(h, I, 0, *fmt.weight(w2), 1, y, N, M, N, I, bias=b2, **_rows_kw(live, True))
         ctx.dims, ctx.lda, ctx.in_shape = (M, K, I, N), lda, x.shape
-        ctx.live = _live_for(M, fmt) if need_grad else None
+        ctx.live = live if need_grad else None
         ctx.targets = (_targets_of(w1), _targets_of(w2), _targets_of(b1), _targets_of(b2))
         ctx.save_for_backward(x2, w1, w2, z, None if ctx.recompute_h else h)
         out = y.view(*x.shape[:-1], N)
@@ -880,7 +912,7 @@ class FFNFn(torch.autograd.Function):
         db1 = _direct_grad(ctx.targets[2], (I,))
         if db1 is None:
             db1 = torch.empty(I, dtype=torch.float32, device=dev)
-        fmt.gemm(dy, ldy, 0, *fmt.weight(w2), 0, dz, I, M, I, N, aux=z, ldaux=I, epi=EPI_MUL_DGELU)   # dH * gelu'(z)
+        fmt.gemm(dy, ldy, 0, *fmt.weight(w2), 0, dz, I, M, I, N, aux=z, ldaux=I, epi=EPI_MUL_DGELU, **_rows_kw(ctx.live))   # dH * gelu'(z)
         dw2 = _direct_grad(ctx.targets[1], (N, I))
         if dw2 is None:
             dw2 = torch.empty((N, I), dtype=torch.float32, device=dev)
@@ -897,11 +929,11 @@ class FFNFn(torch.autograd.Function):
             w, ldw = fmt.weight(w1)
             acc = fmt.accumulate_target(dres, M, K, dy, dy_in)      # (dy is consumed by now, but it may be retained / hooked upstream)
             if acc is not None:          # the residual around the FFN: accumulate into its gradient (see LinearFn)
-                fmt.gemm(dz, I, 0, w, ldw, 0, acc, K, M, K, I, beta=1.0)
+                fmt.gemm(dz, I, 0, w, ldw, 0, acc, K, M, K, I, beta=1.0, **_rows_kw(ctx.live))
                 dx = acc.view(ctx.in_shape)
             else:
                 dx = fmt.empty(M, K, dev)
-                fmt.gemm(dz, I, 0, w, ldw, 0, dx, K, M, K, I)
+                fmt.gemm(dz, I, 0, w, ldw, 0, dx, K, M, K, I, **_rows_kw(ctx.live))
                 dx = dx.view(ctx.in_shape)
                 if dres is not None:
                     dx = dx + dres.reshape(ctx.in_shape)

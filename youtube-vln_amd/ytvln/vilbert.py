@@ -118,6 +118,29 @@ def _live(side: int):
     return contextlib.nullcontext() if live is None or live[side] is None else ops.live_rows_scope(live[side])
 
 
+class _RowsHint:
+    """The host's guess of one side's valid-row count (BertModel.rows_hint).  step(count) returns the guess for this forward and, when not
+    capturing, posts `count` (device int32 [1]) for a later one: a non-blocking copy into pinned memory with an event behind it.  A forward that
+    finds the event complete takes the value, rounded up to 256 rows; under capture the last value is used and nothing is posted or queried."""
+
+    def __init__(self):
+        self.value, self.pinned, self.event = 0, None, None
+
+    def step(self, count) -> int:
+        if torch.cuda.is_current_stream_capturing():
+            return self.value
+        if self.event is not None and self.event.query():
+            self.value = -(-int(self.pinned[0]) // 256) * 256
+            self.event = None
+        if self.event is None:          # (one copy in flight at a time: the pinned word is read only behind its event)
+            if self.pinned is None:
+                self.pinned = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self.pinned.copy_(count, non_blocking=True)
+            self.event = torch.cuda.Event()
+            self.event.record()
+        return self.value
+
+
 def _plan(side: int):
     """The RowsPlan of the text (0) / image (1) stream when its hidden states are packed rows [1, capacity, H], else None."""
     return None if _Runtime.plans is None else _Runtime.plans[side]
@@ -1105,6 +1128,17 @@ class BertModel(BertPreTrainedModel):
     # pre-training losses (ignore_index / target masks), so the pre-training model (Lily) switches it on for its encoder; a bare BertModel and
     # the models that hand per-row outputs to arbitrary losses (VILBertForVLTasks) keep the plain launches.
     wgrad_live_rows = False
+    # Run-time option GEMM_LIVE_M: under the same premise the forward and input-gradient GEMMs compute the valid rows only.  Their launch plans
+    # want the row count on the HOST, and the count lives on the device: every eager forward posts a copy of it into pinned memory behind an
+    # event, and the next forward that finds the event complete uses the value, rounded up to 256 rows (_RowsHint: never a sync, never a wait; a
+    # wrong guess costs time, not rows).  `rows_hint` = (text, image) pins the guesses instead (tests, experiments); None = the posted counts.
+    rows_hint = None
+    _rows_hints = None
+    # The INPUT-GRADIENT GEMMs take the list whenever it exists: dY is zero on a padded row, so dX is what it was, bit for bit.  The FORWARD
+    # GEMMs take it only when this is set (default off, also for Lily): a listed projection returns zeros on its padded rows, and although
+    # no loss reads them they travel row-wise through every later layer into the padded rows of the sequence outputs and of the prediction
+    # scores the model returns -- which callers may look at, and the full-model goldens do.
+    forward_live_rows = False
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
                 co_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
@@ -1136,12 +1170,23 @@ class BertModel(BertPreTrainedModel):
         plan_t, plan_v = self._plans(attention_mask, image_attention_mask)          # (None, None) unless skip_padding is set
         # weight gradients over the valid rows only: one list per padding mask, built here and read by the backward of every projection of that
         # side.  Training with gradients on and padded rows only (packed rows need no list; the pair geometries re-batch one side's rows)
+        # (GEMM_LIVE_M: the same lists carry the permutation that lets the forward and input-gradient GEMMs of the side leave the padded rows
+        #  out, and the host's guess of the count for their launch plans -- _RowsHint)
         self.live_rows = None
+        live_m = ops._lib.option("GEMM_LIVE_M") != 0
         if (self.wgrad_live_rows and self.training and torch.is_grad_enabled() and plan_t is None and plan_v is None and ops.get_matmul_precision() == "fp32"
-                and not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE) and ops._lib.option("GEMM_LIVE_ROWS") != 0):
-            lists = tuple(None if m is None or m.numel() % 32 != 0 else ops.live_rows(m) for m in (attention_mask, image_attention_mask))
+                and not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE) and (ops._lib.option("GEMM_LIVE_ROWS") != 0 or live_m)):
+            lists = tuple(None if m is None or m.numel() % 32 != 0 else ops.live_rows(m, perm=live_m) for m in (attention_mask, image_attention_mask))
             if lists[0] is not None or lists[1] is not None:
                 self.live_rows = lists
+            if live_m:
+                if self._rows_hints is None:
+                    self._rows_hints = (_RowsHint(), _RowsHint())
+                for side, lr in enumerate(lists):
+                    if lr is not None:
+                        fixed = None if self.rows_hint is None else self.rows_hint[side]
+                        lr.forward = bool(self.forward_live_rows)
+                        lr.hint = min(lr.rows, self._rows_hints[side].step(lr.count) if fixed is None else int(fixed))
         try:
             _Runtime.live = self.live_rows
             if not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE):
