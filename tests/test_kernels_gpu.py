@@ -907,3 +907,50 @@ def test_gemm_rowsum_rides_on_the_weight_gradient(dev, lib, M, N, K, expect):
     plain = torch.empty(M, N, device=dev)
     ops._gemm(dY, M, 1, X, N, 0, plain, N, M, N, K)
     assert torch.equal(plain, outs[0][0])
+
+
+# every arm of the tile dispatch of ytvln_gemm_f32, forced through the experiment knobs: (transA, transB, GEMM_TILE, GEMM_SPLITS)
+_TILE_DIMS = [(128, 128), (128, 64), (64, 64), (256, 128), (256, 256), (224, 256), (160, 256)]
+_SWITCH_CASES = ([(0, tb, t, 1) for tb in (1, 0) for t in range(7)] + [(0, tb, t, 2) for tb in (1, 0) for t in (0, 5, 6)] +
+                 [(1, 0, t, 1) for t in (0, 1, 2, 4)] + [(1, 0, t, 2) for t in (0, 4)])
+_SWITCH_OPERANDS = {}
+
+
+def _switch_operands(dev, ta, tb, M, N, K):
+    """(A, B, bias or None, fp64 product) of one layout, made once for all its cases."""
+    key = (ta, tb)
+    if key not in _SWITCH_OPERANDS:
+        A = rnd(dev, *((K, M) if ta else (M, K)), seed=11)
+        B = rnd(dev, *((N, K) if tb else (K, N)), seed=12)
+        bias = None if ta else rnd(dev, N, seed=13)
+        ref = (A.t() if ta else A).double() @ (B.t() if tb else B).double()
+        _SWITCH_OPERANDS[key] = (A, B, bias, ref if bias is None else ref + bias.double())
+    return _SWITCH_OPERANDS[key]
+
+
+@pytest.mark.parametrize("ta,tb,tile,splits", _SWITCH_CASES)
+def test_gemm_tile_dispatch_switch(dev, lib, ta, tb, tile, splits):
+    """ytvln_gemm_f32 with GEMM_TILE / GEMM_SPLITS forced, so that every tile of the dispatch runs in every layout that has it, split and
+    unsplit, whatever the planner would choose for the shape: M = 500 and N = 264 leave a ragged last tile row and column on every tile,
+    K = 1024 is two splits of 512.  The plan is asserted first -- a case must not quietly run 128x128 -- and the entry point is called
+    directly: ops._gemm caches the workspace size by shape, and a size cached before the knobs were set would make a forced split run unsplit."""
+    import ctypes
+    from ytvln import _lib
+    M, N, K = 500, 264, 1024
+    A, B, bias, ref = _switch_operands(dev, ta, tb, M, N, K)
+    prev = (_lib.set_option("GEMM_TILE", tile), _lib.set_option("GEMM_SPLITS", splits))
+    try:
+        tm, tn, sp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        assert _lib.load().ytvln_gemm_plan(M, N, K, ta, 0, ctypes.byref(tm), ctypes.byref(tn), ctypes.byref(sp)) == 0
+        assert (tm.value, tn.value, sp.value) == _TILE_DIMS[tile] + (splits,)
+        need = int(_lib.load().ytvln_gemm_workspace_elems(M, N, K, 0))
+        assert splits == 1 or need >= splits * M * N, need
+        ws = torch.empty(need, device=dev) if need else None
+        C = torch.full((M, N), float("nan"), device=dev)
+        _lib.call("ytvln_gemm_f32", A.data_ptr(), A.stride(0), ta, B.data_ptr(), B.stride(0), tb, C.data_ptr(), N,
+                  bias.data_ptr() if bias is not None else None, None, 0, M, N, K, 0, 0.0, ws.data_ptr() if need else None, need, 0, None)
+        torch.cuda.synchronize()
+    finally:
+        _lib.set_option("GEMM_TILE", prev[0])
+        _lib.set_option("GEMM_SPLITS", prev[1])
+    close(C, ref, 2e-4 * math.sqrt(K / 64) + (0.0 if tb else 1e-5), 1e-4, f"tile {_TILE_DIMS[tile]} x {splits}, transA {ta} transB {tb}")

@@ -620,10 +620,11 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(const float* __restric
 //     tile moves splits x tile bytes at a latency-bound ~50 GB/s while the separate pass uses the whole chip: 119.3 -> 119.7 ms per step
 //     when applied to launches with <= 4 splits, 122.4 with <= 8, 126.2 with all.  profiles/round3_fused_splitk.log.)
 struct Plan { int tile; int splits; };      // tile: 0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 256x128, 4 = 256x256, 5 = 224x256, 6 = 160x256 (3-6: one workgroup per CU)
+struct TileDim { int bm, bn; };
+constexpr TileDim TILE_DIM[7] = {{128, 128}, {128, 64}, {64, 64}, {256, 128}, {256, 256}, {224, 256}, {160, 256}};      // by tile code
 
 static double plan_cost(int M, int N, int K, int tile, int sp, int epilogue = 0, bool x3 = false, bool ta = false) {
     // the two large tiles move fewer operand bytes and LDS fragments per MFMA: ~3 % / ~7 % above the 128x128 rate per CU
-    static const int bm[7] = {128, 128, 64, 256, 256, 224, 160}, bn[7] = {128, 64, 64, 128, 256, 256, 256};
     // us per 32-deep k-tile at the CU-exclusive rate: native fp32 MFMA | three-bf16-term form (fitted on 16128x1024x1024: the split's
     // VALU work is shared best by the wide wave tiles -- 128x128 is VALU-bound, 256x256 matrix-bound)
     // (64x64 and 256x128 exist only for the native instruction: the three-term planner sees their native cost)
@@ -642,7 +643,7 @@ static double plan_cost(int M, int N, int K, int tile, int sp, int epilogue = 0,
     const double* tk = x3 ? tk_x3 : (ta ? tk_f32_ta : tk_f32);
     const int kchunk = (int)cdiv(cdiv(K, sp), BK) * BK;
     const int splits = (int)cdiv(K, kchunk);
-    const double blocks = (double)(cdiv(M, bm[tile]) * cdiv(N, bn[tile])) * splits;
+    const double blocks = (double)(cdiv(M, TILE_DIM[tile].bm) * cdiv(N, TILE_DIM[tile].bn)) * splits;
     const double ncu = (double)sk_num_cus();          // 256 on MI355X (the plans pinned in tests/test_abi.py assume it)
     const double waves = ceil(blocks / ncu);
     // the 4-wave tiles only reach their rate with 2-3 blocks co-resident on a CU (one block = one wave per SIMD)
@@ -670,7 +671,7 @@ static Plan plan_gemm(int M, int N, int K, int epilogue, bool big_ok = false, bo
         if (tile >= 3 && (!big_ok || M < 256)) continue;
         // 224x256: native instruction, K-contiguous A, launches of ONE round (measured: 4480x3072x768 189.7 -> 170.5 us; the 2400-tile LM decoder
         // gains nothing over 2160 tiles of 256x256 -- multi-round launches already overlap their tiles' fixed costs)
-        const int64_t ntile = tile >= 5 ? cdiv(M, tile == 5 ? 224 : 160) * cdiv(N, 256) : 0;
+        const int64_t ntile = tile >= 5 ? cdiv(M, TILE_DIM[tile].bm) * cdiv(N, TILE_DIM[tile].bn) : 0;
         // (M >= 4096: at 2304 rows -- cfg 2 with K = 1 -- the 160-row plans measured 2 % behind the 128x128 ones in the step, 308.7 -> 301.8 rows/s)
         if (tile >= 5 && (x3 || ta || N < 256 || !opt(OPT_GEMM_T224) || (force_tile < 0 && (ntile > sk_num_cus() || M < 4096)))) continue;
         if (ta && tile == 3) continue;          // (256x128 was never measured with an M-contiguous A)
@@ -692,14 +693,17 @@ static Plan plan_gemm(int M, int N, int K, int epilogue, bool big_ok = false, bo
     return best;
 }
 
-static int plan_splits(int M, int N, int K, int epilogue) { return plan_gemm(M, N, K, epilogue).splits; }
+// The grid of a launch with BM x BN tiles: one workgroup per (tile, split); the tile counts go to the kernel.
+static dim3 tile_grid(GemmArgs& g, int bm, int bn) {
+    g.tiles_m = (int)cdiv(g.M, bm);
+    g.tiles_n = (int)cdiv(g.N, bn);
+    g.ntiles = g.tiles_m * g.tiles_n;
+    return dim3(g.ntiles * g.splits);
+}
 
 template <int BM, int BN>
 static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s, const int* live_idx = nullptr, const int* live_count = nullptr) {
-    g.tiles_m = (int)cdiv(g.M, BM);
-    g.tiles_n = (int)cdiv(g.N, BN);
-    g.ntiles = g.tiles_m * g.tiles_n;
-    dim3 grid(g.ntiles * g.splits), block(256);
+    const dim3 grid = tile_grid(g, BM, BN), block(256);
     if (g.fast) {
 #define YT_DMA(NW, KB, NS, WPS)                                                                                                        \
     do {                                                                                                                               \
@@ -739,10 +743,8 @@ static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s, const
             dim3 blk(512);
             if (transB) hipLaunchKernelGGL((gemm_dma_kernel<BM, 256, true, true, 8, 32, 2, 2, false, 8>), grid, blk, 0, s, g);
             else hipLaunchKernelGGL((gemm_dma_kernel<BM, 256, true, false, 8, 32, 2, 2, false, 8>), grid, blk, 0, s, g);
-        } else if constexpr (BM == 256 && BN == 256) {
-            YT_DMA(8, 32, 2, 2);                    // 8 waves of 64x128, one workgroup per CU
-        } else if constexpr (BM == 256 && BN == 128) {
-            YT_DMA(8, 32, 2, 2);                    // 8 waves of 64x64, one workgroup per CU (native instruction only, like 64x64)
+        } else if constexpr (BM == 256) {
+            YT_DMA(8, 32, 2, 2);                    // one workgroup per CU: 8 waves of 64x128 (256x256) or of 64x64 (256x128: native instruction only, like 64x64)
         } else if constexpr (BM == 128 && BN == 128) {
             YT_DMA(8, 32, 2, 4);
         } else {
@@ -765,14 +767,11 @@ static int launch_tile(GemmArgs& g, int transA, int transB, hipStream_t s, const
 // of 128x128 at the live rows).  The 224- / 160-row tiles, the 4-wave tiles and the one-wave-per-SIMD form are not instantiated.
 template <int BM, int BN>
 static void launch_rows_tile(GemmArgs& g, int transB, hipStream_t s, const int* perm, const int* count) {
-    g.tiles_m = (int)cdiv(g.M, BM);          // the grid covers the full M: the count is device data
-    g.tiles_n = (int)cdiv(g.N, BN);
-    g.ntiles = g.tiles_m * g.tiles_n;
+    const dim3 grid = tile_grid(g, BM, BN), blk(512);          // the grid covers the full M: the count is device data
     GemmRowsArgs rg;
     static_cast<GemmArgs&>(rg) = g;
     rg.row_perm = perm; rg.row_count = count;
     constexpr int WPS = BM == 256 ? 2 : 4;
-    const dim3 grid(g.ntiles * g.splits), blk(512);
     if (transB) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, true, true, 8, 32, 2, WPS, false, 2, false, true>), grid, blk, 0, s, rg);
     else hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, true, false, 8, 32, 2, WPS, false, 2, false, true>), grid, blk, 0, s, rg);
 }
@@ -796,33 +795,31 @@ static Plan plan_rows(int M, int N, int K, int epilogue, int m_hint) {
 
 using namespace ytvln;
 
+static int report_plan(const Plan& p, int* tile_m, int* tile_n, int* splits) {
+    *tile_m = TILE_DIM[p.tile].bm; *tile_n = TILE_DIM[p.tile].bn; *splits = p.splits;
+    return 0;
+}
+
 extern "C" int ytvln_gemm_plan(int M, int N, int K, int transA, int epilogue, int* tile_m, int* tile_n, int* splits) {
     YT_REQUIRE(tile_m && tile_n && splits && M > 0 && N > 0 && K > 0, "gemm_plan: bad argument");
-    static const int bm[7] = {128, 128, 64, 256, 256, 224, 160}, bn[7] = {128, 64, 64, 128, 256, 256, 256};
-    const Plan p = plan_gemm(M, N, K, epilogue, true, false, transA != 0);
-    *tile_m = bm[p.tile]; *tile_n = bn[p.tile]; *splits = p.splits;
-    return 0;
+    return report_plan(plan_gemm(M, N, K, epilogue, true, false, transA != 0), tile_m, tile_n, splits);
 }
 
 extern "C" int ytvln_gemm_plan_x3(int M, int N, int K, int transA, int epilogue, int* tile_m, int* tile_n, int* splits) {
     YT_REQUIRE(tile_m && tile_n && splits && M > 0 && N > 0 && K > 0, "gemm_plan_x3: bad argument");
     (void)transA;       // the three-term form takes the 256-row tiles with either A layout (see ytvln_gemm_f32)
-    static const int bm[7] = {128, 128, 64, 256, 256, 224, 160}, bn[7] = {128, 64, 64, 128, 256, 256, 256};
-    const Plan p = plan_gemm(M, N, K, epilogue, true, true);
-    *tile_m = bm[p.tile]; *tile_n = bn[p.tile]; *splits = p.splits;
-    return 0;
+    return report_plan(plan_gemm(M, N, K, epilogue, true, true), tile_m, tile_n, splits);
 }
 
 #if YT_GEMM_PROBE
 extern "C" int ytvln_gemm_f32_probe_read(uint32_t* host128) { return hipMemcpyFromSymbol(host128, HIP_SYMBOL(g_f32_probe), 512) == hipSuccess ? 0 : -1; }
 #endif
 extern "C" int64_t ytvln_gemm_workspace_elems(int M, int N, int K, int epilogue) {
-    const int splits = std::max(std::max(std::max(std::max(plan_splits(M, N, K, epilogue), plan_gemm(M, N, K, epilogue, true, false, false).splits),
-                                                  plan_gemm(M, N, K, epilogue, true, false, true).splits),
-                                         std::max(plan_gemm(M, N, K, epilogue, false, true).splits,
-                                                  plan_gemm(M, N, K, epilogue, true, true).splits)),
-                                1);
-    // (covers either A layout and the fp32x3 plans)
+    // the plans a launch of this shape may take: the generic kernel's, either A layout on the LDS-DMA path, the two fp32x3 ones
+    static const struct { bool big_ok, x3, ta; } variants[5] = {{false, false, false}, {true, false, false}, {true, false, true},
+                                                                {false, true, false}, {true, true, false}};
+    int splits = 1;
+    for (const auto& v : variants) splits = std::max(splits, plan_gemm(M, N, K, epilogue, v.big_ok, v.x3, v.ta).splits);
     int64_t need = splits > 1 ? (int64_t)splits * M * N + (int64_t)splits * ((M + 3) / 4 * 4) : 0;      // partial tiles + partial row sums of A
     // the stream-K form of the persistent kernel (K-contiguous A; opt-in GEMM_SK): one partial tile per workgroup, sized for either tile.
     // Only while the option is on (134 MB per GEMM for a kernel that is off by default); a caller that caches the figure keys it
@@ -831,39 +828,52 @@ extern "C" int64_t ytvln_gemm_workspace_elems(int M, int N, int K, int epilogue)
     return need;
 }
 
-static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
-                         int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K,
-                         int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum, int* rowsum_done,
-                         unsigned* sk_ctl, void* stream, const int* live_idx = nullptr, const int* live_count = nullptr,
-                         const int* row_perm = nullptr, const int* row_count = nullptr, int m_hint = 0) {
-    if (rowsum_done) *rowsum_done = 0;
-    YT_REQUIRE(A && B && C, "gemm: null operand");
+// The kernel of a plan's tile, split or not.  No fallbacks: plan_gemm hands out tiles 5 and 6 only with big_ok && !x3 && !ta, which gemm_f32_impl passes
+// as g.fast, g.x3 && g.fast and g.fast && transA && !g.x3 -- the native LDS-DMA path with a K-contiguous A (a forced GEMM_TILE skips the other candidates,
+// not that test; the re-plan of a launch without workspace picks among tiles 0-2) -- and more than one split only to tiles 0, 4, 5 and 6 (smax).
+static void launch_plan_tile(int tile, GemmArgs& g, int transA, int transB, hipStream_t s, const int* live_idx, const int* live_count);          // (defined behind gemm_f32_impl: the row-listed kernels are still instantiated first, the code object keeps its order)
+
+// What one ytvln_gemm_f32* call asks for: the arguments every entry point takes, in the order of the ABI, then the optional features (off unless set by name).
+struct GemmCall {
+    const float* A; int64_t lda; int transA; const float* B; int64_t ldb; int transB; float* C; int64_t ldc;
+    const float* bias; float* aux; int64_t ldaux; int M, N, K, epilogue; float beta;
+    float* workspace; int64_t workspace_elems; int flags; void* stream;
+    float* a_rowsum = nullptr; int* rowsum_done = nullptr;          // row sums of op(A) riding on the launch (ytvln_gemm_f32_rowsum)
+    unsigned* sk_ctl = nullptr;                                     // control block of the persistent kernel (ytvln_gemm_f32_sk)
+    const int* live_idx = nullptr; const int* live_count = nullptr; // rows the contraction runs over (ytvln_gemm_f32_live)
+    const int* row_perm = nullptr; const int* row_count = nullptr; int m_hint = 0;          // rows of C to compute, the host's guess of their number (ytvln_gemm_f32_rows)
+};
+
+static int gemm_f32_impl(const GemmCall& c) {
+    const int M = c.M, N = c.N, K = c.K, transA = c.transA, transB = c.transB;
+    if (c.rowsum_done) *c.rowsum_done = 0;
+    YT_REQUIRE(c.A && c.B && c.C, "gemm: null operand");
     YT_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
-    YT_REQUIRE(epilogue >= YTVLN_EPI_NONE && epilogue <= YTVLN_EPI_MUL_DRELU, "gemm: bad epilogue %d", epilogue);
-    YT_REQUIRE(!(epilogue >= YTVLN_EPI_MUL_DGELU) || aux, "gemm: epilogue %d needs aux", epilogue);
-    YT_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "gemm: leading dimension too small");
+    YT_REQUIRE(c.epilogue >= YTVLN_EPI_NONE && c.epilogue <= YTVLN_EPI_MUL_DRELU, "gemm: bad epilogue %d", c.epilogue);
+    YT_REQUIRE(!(c.epilogue >= YTVLN_EPI_MUL_DGELU) || c.aux, "gemm: epilogue %d needs aux", c.epilogue);
+    YT_REQUIRE(c.lda >= (transA ? M : K) && c.ldb >= (transB ? K : N) && c.ldc >= N, "gemm: leading dimension too small");
     if (M == 0 || N == 0) return 0;
     GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux;
-    g.M = M; g.N = N; g.K = K; g.epilogue = epilogue; g.beta = beta;
-    g.vecA = ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && (lda % 4 == 0);
-    g.vecB = ((reinterpret_cast<uintptr_t>(B) & 15) == 0) && (ldb % 4 == 0);
-    hipStream_t s = as_stream(stream);
+    g.A = c.A; g.B = c.B; g.C = c.C; g.bias = c.bias; g.aux = c.aux;
+    g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.ldaux = c.ldaux;
+    g.M = M; g.N = N; g.K = K; g.epilogue = c.epilogue; g.beta = c.beta;
+    g.vecA = ((reinterpret_cast<uintptr_t>(c.A) & 15) == 0) && (c.lda % 4 == 0);
+    g.vecB = ((reinterpret_cast<uintptr_t>(c.B) & 15) == 0) && (c.ldb % 4 == 0);
+    hipStream_t s = as_stream(c.stream);
     g.splits = 1; g.kchunk = K; g.ws = nullptr;
-    g.x3 = (flags & YTVLN_GEMM_SPLIT_BF16X3) != 0;
+    g.x3 = (c.flags & YTVLN_GEMM_SPLIT_BF16X3) != 0;
     g.split_map = opt(OPT_GEMM_SPLIT_MAP);
     g.asum = nullptr; g.asum_ws = nullptr;
     // Fast-path legality.  With YTVLN_GEMM_A_ZERO_PADDED the caller guarantees that A's contiguous dimension is followed by
     // readable ZERO padding up to lda: a K-contiguous A may then have K % 32 != 0 (the loop runs over the rounded-up K and
     // B's k rows are clamped -- B must be [K,N]), and an M-contiguous A may have M % 4 != 0.
-    const bool apad = (flags & YTVLN_GEMM_A_ZERO_PADDED) != 0;
+    const bool apad = (c.flags & YTVLN_GEMM_A_ZERO_PADDED) != 0;
     const int k32 = (int)cdiv(K, BK) * BK, m4 = (int)cdiv(M, 4) * 4;
     g.Kloop = K; g.ktail = 0; g.mnA = M; g.mnB = N;
     bool k_ok = (K % BK == 0);
-    if (!k_ok && apad && !transA && !transB && lda >= k32) { k_ok = true; g.Kloop = k32; g.ktail = 1; }
+    if (!k_ok && apad && !transA && !transB && c.lda >= k32) { k_ok = true; g.Kloop = k32; g.ktail = 1; }
     bool ma_ok = !transA || (M % 4 == 0 && M >= 4);
-    if (!ma_ok && apad && transA && lda >= m4 && M >= 4) { ma_ok = true; g.mnA = m4; }
+    if (!ma_ok && apad && transA && c.lda >= m4 && M >= 4) { ma_ok = true; g.mnA = m4; }
     g.fast = (K > 0) && k_ok && g.vecA && g.vecB && ma_ok && (!transB ? (N % 4 == 0 && N >= 4) : true) &&
              !opt(OPT_GEMM_GENERIC);
     // row-listed launch (GEMM_LIVE_M): K-contiguous A on the native LDS-DMA loop, whole k-tiles.  The tile is chosen for m_hint rows (0 = M) among
@@ -873,53 +883,47 @@ static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B
     // The opt-in forms (persistent kernel, one-wave-per-SIMD kernel) and a GEMM_TILE forced to a tile that has no listed form launch what they
     // launch today.
     const int ftile = opt(OPT_GEMM_TILE);
-    const bool rows_form = row_perm && row_count && opt(OPT_GEMM_LIVE_M) != 0 && g.fast && !transA && !g.x3 && !g.ktail && K % BK == 0 && !a_rowsum &&
+    auto split_k = [&](int n) { g.kchunk = (int)cdiv(cdiv(K, n), BK) * BK; g.splits = (int)cdiv(K, g.kchunk); g.ws = c.workspace; };
+    const bool rows_form = c.row_perm && c.row_count && opt(OPT_GEMM_LIVE_M) != 0 && g.fast && !transA && !g.x3 && !g.ktail && K % BK == 0 && !c.a_rowsum &&
                            opt(OPT_GEMM_SK) == 0 && opt(OPT_GEMM_SW) == 0 && (ftile < 0 || ftile == 0 || ftile == 4);
-    const Plan rplan = rows_form ? plan_rows(M, N, K, epilogue, m_hint) : Plan{0, 1};
+    const Plan rplan = rows_form ? plan_rows(M, N, K, c.epilogue, c.m_hint) : Plan{0, 1};
     // split-K: partials by list position, reduced by rows_reduce_kernel in 16-byte pieces of a row -- N % 4 == 0 (B = [N, K] may have any N),
     // aligned rows of C, and the workspace.  A split launch without them stays unlisted rather than change its split count.
-    const bool red_ok = N % 4 == 0 && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && workspace &&
-                        workspace_elems >= (int64_t)rplan.splits * M * N;
+    const bool red_ok = N % 4 == 0 && c.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(c.C) & 15) == 0 && c.workspace &&
+                        c.workspace_elems >= (int64_t)rplan.splits * M * N;
     if (rows_form && (rplan.splits == 1 || red_ok)) {
-        const Plan plan = rplan;
-        if (plan.splits > 1) {
-            g.kchunk = (int)cdiv(cdiv(K, plan.splits), BK) * BK;
-            g.splits = (int)cdiv(K, g.kchunk);
-            g.ws = workspace;
-        }
+        if (rplan.splits > 1) split_k(rplan.splits);
         if (g.splits == 1) g.kchunk = std::max(g.kchunk, g.Kloop);
-        if (plan.tile == 4) launch_rows_tile<256, 256>(g, transB, s, row_perm, row_count);
-        else launch_rows_tile<128, 128>(g, transB, s, row_perm, row_count);
+        if (rplan.tile == 4) launch_rows_tile<256, 256>(g, transB, s, c.row_perm, c.row_count);
+        else launch_rows_tile<128, 128>(g, transB, s, c.row_perm, c.row_count);
         if (g.splits > 1)
-            hipLaunchKernelGGL(rows_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)M * N, 1024), 2048)), dim3(256), 0, s, workspace, C, ldc,
-                               bias, M, N, g.splits, beta, row_perm, row_count);
+            hipLaunchKernelGGL(rows_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)M * N, 1024), 2048)), dim3(256), 0, s, c.workspace, c.C, c.ldc,
+                               c.bias, M, N, g.splits, c.beta, c.row_perm, c.row_count);
         YT_LAUNCH_CHECK("gemm_f32 (row list)");
         return 0;
     }
     // the 256-row tiles take either A layout: K-contiguous (forward / input gradients) and M-contiguous (weight gradients; 256x256 + split-K
     // competes with 128x128 since round 2), in the native and in the three-term form
     const bool ta_native = g.fast && transA && !g.x3;
-    Plan plan = plan_gemm(M, N, K, epilogue, g.fast, g.x3 && g.fast, ta_native);
+    Plan plan = plan_gemm(M, N, K, c.epilogue, g.fast, g.x3 && g.fast, ta_native);
     const int want = plan.splits;
     // persistent kernel (gemm_sk.hip): needs the caller's zero-initialised control block; taken when its model cost beats the launch-per-tile plan
-    if (sk_ctl && !a_rowsum) {
-        SkPlan sp = plan_sk(M, N, g.Kloop, transA, epilogue, g.fast, g.x3 != 0);
-        if (sp.use && !sp.dp && (!workspace || workspace_elems < sk_workspace_elems(sp))) sp.use = 0;
-        if (sp.use && (opt(OPT_GEMM_SK) >= 2 || sp.cost < 0.98 * plan_cost(M, N, K, plan.tile, plan.splits, epilogue, false, ta_native))) {
-            sk_launch(g, sp, transB, workspace, sk_ctl, s);
+    if (c.sk_ctl && !c.a_rowsum) {
+        SkPlan sp = plan_sk(M, N, g.Kloop, transA, c.epilogue, g.fast, g.x3 != 0);
+        if (sp.use && !sp.dp && (!c.workspace || c.workspace_elems < sk_workspace_elems(sp))) sp.use = 0;
+        if (sp.use && (opt(OPT_GEMM_SK) >= 2 || sp.cost < 0.98 * plan_cost(M, N, K, plan.tile, plan.splits, c.epilogue, false, ta_native))) {
+            sk_launch(g, sp, transB, c.workspace, c.sk_ctl, s);
             YT_LAUNCH_CHECK("gemm_f32 (persistent)");
             return 0;
         }
     }
     // row sums of op(A) ride on launches that take the LDS-DMA main loop with an M-contiguous fp32 A and no K tail (a clamped tail row would
     // be counted twice); everything else reports "not done" and the caller runs ytvln_colsum_f32
-    const bool asum_ok = a_rowsum && g.fast && transA && !g.x3 && !g.ktail && K % BK == 0;
+    const bool asum_ok = c.a_rowsum && g.fast && transA && !g.x3 && !g.ktail && K % BK == 0;
     const int64_t m4r = (M + 3) / 4 * 4;
-    if (want > 1 && workspace && workspace_elems >= (int64_t)want * M * N + (asum_ok ? (int64_t)want * m4r : 0)) {
-        g.kchunk = (int)cdiv(cdiv(K, want), BK) * BK;
-        g.splits = (int)cdiv(K, g.kchunk);
-        g.ws = workspace;
-        if (asum_ok) { g.asum = a_rowsum; g.asum_ws = workspace + (int64_t)g.splits * M * N; }
+    if (want > 1 && c.workspace && c.workspace_elems >= (int64_t)want * M * N + (asum_ok ? (int64_t)want * m4r : 0)) {
+        split_k(want);
+        if (asum_ok) { g.asum = c.a_rowsum; g.asum_ws = c.workspace + (int64_t)g.splits * M * N; }
     } else if (want > 1) {                 // no workspace supplied: best unsplit plan
         plan.splits = 1;
         double bt = 1e30;
@@ -929,42 +933,35 @@ static int gemm_f32_impl(const float* A, int64_t lda, int transA, const float* B
         }
     }
     if (g.splits == 1) g.kchunk = std::max(g.kchunk, g.Kloop);
-    if (g.splits == 1 && asum_ok) g.asum = a_rowsum;
-    if (rowsum_done) *rowsum_done = g.asum != nullptr;
+    if (g.splits == 1 && asum_ok) g.asum = c.a_rowsum;
+    if (c.rowsum_done) *c.rowsum_done = g.asum != nullptr;
     // live-row contraction (GEMM_LIVE_ROWS): both operands k-major on the native LDS-DMA loop, whole 32-row k-tiles, a K-chunk whose list slice
     // fits the LDS behind the ring, byte pitches below 2^32; the kernels exist for the 256x256 and 128x128 tiles (launch_tile).  Anything else
     // runs the plain launch: the listed-out rows of A are zero, so the result is the same sum.
-    if (!(live_idx && live_count && opt(OPT_GEMM_LIVE_ROWS) != 0 && g.fast && transA && !transB && !g.x3 && !g.ktail && K % BK == 0 &&
-          g.kchunk <= LIVE_CAP && lda < ((int64_t)1 << 30) && ldb < ((int64_t)1 << 30)))
-        live_idx = live_count = nullptr;
-    if (g.splits > 1) {
-        if (plan.tile == 4) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
-        else if (plan.tile == 5 && g.fast && !transA && !g.x3) launch_tile<224, 256>(g, transA, transB, s);
-        else if (plan.tile == 6 && g.fast && !transA && !g.x3) launch_tile<160, 256>(g, transA, transB, s);
-        else launch_tile<128, 128>(g, transA, transB, s, live_idx, live_count);
-        const int64_t total = (int64_t)M * N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 1024), 2048)), dim3(256), 0, s, workspace, C,
-                           ldc, bias, M, N, g.splits, beta, (const float*)g.asum_ws, g.asum);
-    } else {
-        g.splits = 1;
-        if (plan.tile == 4) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
-        else if (plan.tile == 5 && g.fast && !transA && !g.x3) launch_tile<224, 256>(g, transA, transB, s);
-        else if (plan.tile == 6 && g.fast && !transA && !g.x3) launch_tile<160, 256>(g, transA, transB, s);
-        else if (plan.tile >= 5) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
-        else if (plan.tile == 3) launch_tile<256, 128>(g, transA, transB, s);
-        else if (plan.tile == 0) launch_tile<128, 128>(g, transA, transB, s, live_idx, live_count);
-        else if (plan.tile == 1) launch_tile<128, 64>(g, transA, transB, s);
-        else launch_tile<64, 64>(g, transA, transB, s);
-    }
+    const bool live = c.live_idx && c.live_count && opt(OPT_GEMM_LIVE_ROWS) != 0 && g.fast && transA && !transB && !g.x3 && !g.ktail && K % BK == 0 &&
+                      g.kchunk <= LIVE_CAP && c.lda < ((int64_t)1 << 30) && c.ldb < ((int64_t)1 << 30);
+    launch_plan_tile(plan.tile, g, transA, transB, s, live ? c.live_idx : nullptr, live ? c.live_count : nullptr);
+    if (g.splits > 1)
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)M * N, 1024), 2048)), dim3(256), 0, s, c.workspace, c.C,
+                           c.ldc, c.bias, M, N, g.splits, c.beta, (const float*)g.asum_ws, g.asum);
     YT_LAUNCH_CHECK("gemm_f32");
     return 0;
+}
+
+static void launch_plan_tile(int tile, GemmArgs& g, int transA, int transB, hipStream_t s, const int* live_idx, const int* live_count) {
+    if (tile == 4) launch_tile<256, 256>(g, transA, transB, s, live_idx, live_count);
+    else if (tile == 5) launch_tile<224, 256>(g, transA, transB, s);
+    else if (tile == 6) launch_tile<160, 256>(g, transA, transB, s);
+    else if (tile == 0) launch_tile<128, 128>(g, transA, transB, s, live_idx, live_count);
+    else if (tile == 3) launch_tile<256, 128>(g, transA, transB, s);
+    else if (tile == 1) launch_tile<128, 64>(g, transA, transB, s);
+    else launch_tile<64, 64>(g, transA, transB, s);
 }
 
 extern "C" int ytvln_gemm_f32(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
                               int64_t ldc, const float* bias, float* aux, int64_t ldaux, int M, int N, int K,
                               int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, void* stream) {
-    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
-                         nullptr, nullptr, nullptr, stream);
+    return gemm_f32_impl(GemmCall{A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags, stream});
 }
 
 extern "C" int ytvln_gemm_f32_rowsum(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
@@ -972,8 +969,9 @@ extern "C" int ytvln_gemm_f32_rowsum(const float* A, int64_t lda, int transA, co
                                      int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum,
                                      int* rowsum_done, void* stream) {
     YT_REQUIRE(a_rowsum && rowsum_done, "gemm_f32_rowsum: null row-sum output");
-    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
-                         a_rowsum, rowsum_done, nullptr, stream);
+    GemmCall c{A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags, stream};
+    c.a_rowsum = a_rowsum; c.rowsum_done = rowsum_done;
+    return gemm_f32_impl(c);
 }
 
 extern "C" int ytvln_gemm_f32_sk(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
@@ -981,8 +979,9 @@ extern "C" int ytvln_gemm_f32_sk(const float* A, int64_t lda, int transA, const 
                                  int epilogue, float beta, float* workspace, int64_t workspace_elems, int flags, float* a_rowsum,
                                  int* rowsum_done, uint32_t* sk_ctl, void* stream) {
     YT_REQUIRE((a_rowsum == nullptr) == (rowsum_done == nullptr), "gemm_f32_sk: a_rowsum and rowsum_done go together");
-    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
-                         a_rowsum, rowsum_done, sk_ctl, stream);
+    GemmCall c{A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags, stream};
+    c.a_rowsum = a_rowsum; c.rowsum_done = rowsum_done; c.sk_ctl = sk_ctl;
+    return gemm_f32_impl(c);
 }
 
 extern "C" int ytvln_gemm_f32_live(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
@@ -991,8 +990,9 @@ extern "C" int ytvln_gemm_f32_live(const float* A, int64_t lda, int transA, cons
                                    int* rowsum_done, const int* live_idx, const int* live_count, void* stream) {
     YT_REQUIRE((a_rowsum == nullptr) == (rowsum_done == nullptr), "gemm_f32_live: a_rowsum and rowsum_done go together");
     YT_REQUIRE(live_idx && live_count, "gemm_f32_live: null row list");
-    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
-                         a_rowsum, rowsum_done, nullptr, stream, live_idx, live_count);
+    GemmCall c{A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags, stream};
+    c.a_rowsum = a_rowsum; c.rowsum_done = rowsum_done; c.live_idx = live_idx; c.live_count = live_count;
+    return gemm_f32_impl(c);
 }
 
 extern "C" int ytvln_gemm_f32_rows(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C,
@@ -1001,8 +1001,9 @@ extern "C" int ytvln_gemm_f32_rows(const float* A, int64_t lda, int transA, cons
                                    const int* row_perm, const int* row_count, int m_hint, void* stream) {
     YT_REQUIRE(row_perm && row_count, "gemm_f32_rows: null row list");
     YT_REQUIRE(m_hint >= 0, "gemm_f32_rows: negative m_hint %d", m_hint);
-    return gemm_f32_impl(A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags,
-                         nullptr, nullptr, nullptr, stream, nullptr, nullptr, row_perm, row_count, m_hint);
+    GemmCall c{A, lda, transA, B, ldb, transB, C, ldc, bias, aux, ldaux, M, N, K, epilogue, beta, workspace, workspace_elems, flags, stream};
+    c.row_perm = row_perm; c.row_count = row_count; c.m_hint = m_hint;
+    return gemm_f32_impl(c);
 }
 
 extern "C" int64_t ytvln_gemm_rows_workspace_elems(int M, int N, int K, int epilogue, int m_hint) {
@@ -1016,9 +1017,7 @@ extern "C" int64_t ytvln_gemm_rows_workspace_elems(int M, int N, int K, int epil
 
 extern "C" int ytvln_gemm_rows_plan(int M, int N, int K, int epilogue, int m_hint, int* tile_m, int* tile_n, int* splits) {
     YT_REQUIRE(tile_m && tile_n && splits && M > 0 && N > 0 && K > 0 && m_hint >= 0, "gemm_rows_plan: bad argument");
-    const Plan p = plan_rows(M, N, K, epilogue, m_hint);
-    *tile_m = *tile_n = p.tile == 4 ? 256 : 128; *splits = p.splits;
-    return 0;
+    return report_plan(plan_rows(M, N, K, epilogue, m_hint), tile_m, tile_n, splits);
 }
 
 extern "C" int ytvln_gemm_sk_plan(int M, int N, int K, int transA, int epilogue, int* use, int* tile_m, int* tile_n, int* whole_tiles,
@@ -1027,7 +1026,7 @@ extern "C" int ytvln_gemm_sk_plan(int M, int N, int K, int transA, int epilogue,
     const SkPlan sp = plan_sk(M, N, (int)cdiv(K, BK) * BK, transA, epilogue, true, false);
     const Plan plan = plan_gemm(M, N, K, epilogue, true, false, transA != 0);
     *use = sp.use && (opt(OPT_GEMM_SK) >= 2 || sp.cost < 0.98 * plan_cost(M, N, K, plan.tile, plan.splits, epilogue, false, transA != 0));
-    *tile_m = sp.tile == 0 ? 128 : 256; *tile_n = sp.tile == 4 ? 256 : 128; *whole_tiles = sp.dp; *workgroups = sp.G;
+    *tile_m = TILE_DIM[sp.tile].bm; *tile_n = TILE_DIM[sp.tile].bn; *whole_tiles = sp.dp; *workgroups = sp.G;          // (SkPlan uses the same tile codes)
     return 0;
 }
 

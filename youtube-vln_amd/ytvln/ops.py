@@ -316,38 +316,31 @@ def _gemm(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias=None, aux=None, 
     forward / input-gradient launch (transA = 0) computes: the rows behind the count come back as zeros (beta = 0) or untouched
     (ytvln_gemm_f32_rows); a hint equal to M means "every row is expected to be listed" and launches the plain form."""
     sk = _lib.option("GEMM_SK") != 0          # the persistent kernel (opt-in): its partial-tile scratch and control block exist only then
-    if (rows is not None and rows.perm is not None and not transA and rows.rows == M and rows.hint < M and rowsum is None
-            and _MATMUL_PRECISION == "fp32"):
-        key = (M, N, K, epi, sk, "rows", rows.hint)
-        need = _WS_CACHE.get(key)
-        if need is None:
-            need = _WS_CACHE[key] = int(_lib.load().ytvln_gemm_rows_workspace_elems(M, N, K, epi, rows.hint))
-        ws = torch.empty(need, dtype=torch.float32, device=C.device) if need else None
-        call("ytvln_gemm_f32_rows", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
-             M, N, K, epi, float(beta), _ptr(ws), need, int(flags), rows.perm.data_ptr(), rows.count.data_ptr(), rows.hint, _stream())
-        return False
-    key = (M, N, K, epi, sk)
+    by_rows = (rows is not None and rows.perm is not None and not transA and rows.rows == M and rows.hint < M and rowsum is None
+               and _MATMUL_PRECISION == "fp32")
+    key = (M, N, K, epi, sk, "rows", rows.hint) if by_rows else (M, N, K, epi, sk)
     need = _WS_CACHE.get(key)
     if need is None:
-        need = _WS_CACHE[key] = int(_lib.load().ytvln_gemm_workspace_elems(M, N, K, epi))
+        lib = _lib.load()
+        need = _WS_CACHE[key] = int(lib.ytvln_gemm_rows_workspace_elems(M, N, K, epi, rows.hint) if by_rows
+                                    else lib.ytvln_gemm_workspace_elems(M, N, K, epi))
     ws = torch.empty(need, dtype=torch.float32, device=C.device) if need else None      # split-K / stream-K scratch (caching allocator)
-    if _MATMUL_PRECISION == "fp32x3":
+    if _MATMUL_PRECISION == "fp32x3":          # (never a row-listed launch: those are fp32 only)
         flags = int(flags) | GEMM_SPLIT_BF16X3
+    # the arguments every entry point starts with
+    head = (_ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux, M, N, K, epi, float(beta),
+            _ptr(ws), need, int(flags))
+    if by_rows:
+        call("ytvln_gemm_f32_rows", *head, rows.perm.data_ptr(), rows.count.data_ptr(), rows.hint, _stream())
+        return False
     ctl = _sk_ctl(C.device) if sk else None
+    done = ctypes.c_int(0)
+    rowsum_out = (_ptr(rowsum), ctypes.byref(done) if rowsum is not None else None)
     if live is not None and transA and not transB and live.rows == K and _MATMUL_PRECISION == "fp32":
-        done = ctypes.c_int(0)
-        call("ytvln_gemm_f32_live", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
-             M, N, K, epi, float(beta), _ptr(ws), need, int(flags), _ptr(rowsum), ctypes.byref(done) if rowsum is not None else None,
-             live.idx.data_ptr(), live.count.data_ptr(), _stream())
-        return bool(done.value)
-    if rowsum is not None:
-        done = ctypes.c_int(0)
-        call("ytvln_gemm_f32_sk", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
-             M, N, K, epi, float(beta), _ptr(ws), need, int(flags), _ptr(rowsum), ctypes.byref(done), _ptr(ctl), _stream())
-        return bool(done.value)
-    call("ytvln_gemm_f32_sk", _ptr(A), lda, int(transA), _ptr(B), ldb, int(transB), _ptr(C), ldc, _ptr(bias), _ptr(aux), ldaux,
-         M, N, K, epi, float(beta), _ptr(ws), need, int(flags), None, None, _ptr(ctl), _stream())
-    return False
+        call("ytvln_gemm_f32_live", *head, *rowsum_out, live.idx.data_ptr(), live.count.data_ptr(), _stream())
+    else:
+        call("ytvln_gemm_f32_sk", *head, *rowsum_out, _ptr(ctl), _stream())
+    return bool(done.value)
 
 
 class LiveRows:
@@ -533,6 +526,12 @@ def _direct_grad(targets, shape):
     for t in targets:
         first.written.add(t._ytvln_slot.off)
     return first.flat_g[first.off:off].view(shape)
+
+
+def _grad_buffer(targets, shape, device) -> Tensor:
+    """Where a weight or bias gradient is written: its gradient-arena view (`_direct_grad`), or a fresh fp32 buffer."""
+    g = _direct_grad(targets, shape)
+    return g if g is not None else torch.empty(shape, dtype=torch.float32, device=device)
 
 
 class PackRowsFn(torch.autograd.Function):
@@ -740,6 +739,43 @@ def _alloc_rows_bf16(M: int, N: int, device):
     return _B16.alloc_rows(M, N, device, kernel_zeroes_pad=True)
 
 
+def _input_grad(fmt, dy, ldy, flags, weight, dims, dres, keep, in_shape, live, as_f32=False):
+    """dX = dY W (+ dres), viewed as `in_shape`, for y = x W^T with dims = (M, K, N): dY is [M, N] rows of `fmt` with leading dimension `ldy` and
+    GEMM `flags`, W the [N, K] master weight.  `dres` is the gradient of the residual branch that skips the sublayer (or None): the GEMM
+    accumulates into it (beta = 1) when `fmt.accumulate_target` allows -- `keep` are the tensors that rule treats as live -- else the product gets
+    its own buffer and an add follows; `as_f32` (an fp32 input of the bf16-resident path) then lets the gradient leave as fp32.  `live`: the
+    LiveRows of the scope, or None (the launch computes the listed rows only where the list has `perm`)."""
+    M, K, N = dims
+    w, ldw = fmt.weight(weight)
+    acc = fmt.accumulate_target(dres, M, K, *keep)
+    if acc is not None:          # dx = d(residual) + dY W, written over the residual branch's gradient
+        fmt.gemm(dy, ldy, 0, w, ldw, 0, acc, K, M, K, N, beta=1.0, flags=flags, **_rows_kw(live))
+        return acc.view(in_shape)
+    dx = fmt.empty(M, K, dy.device)
+    fmt.gemm(dy, ldy, 0, w, ldw, 0, dx, K, M, K, N, flags=flags, **_rows_kw(live))
+    dx = dx.view(in_shape)
+    if dres is not None:
+        dx = dx + dres.reshape(in_shape)
+    return dx.float() if as_f32 else dx
+
+
+def _weight_grads(fmt, dy, ldy, flags, x2, ldx, dims, wtargets, btargets, live, want_dw=True, want_db=True):
+    """(dW [N, K], db [N]) of y = x W^T + b with dims = (M, N, K), fp32 in either format, each in its gradient-arena slot where it has one
+    (`_grad_buffer`); None for the one not wanted.  dW = dY^T X contracts over the rows of `live` (LiveRows or None); db = the column sums of
+    dY = the row sums of that launch's A operand rides on it (`rowsum`) and falls back to `colsum` where the launch reports "not done" -- or
+    where there is no launch, the bias gradient being the only one wanted."""
+    M, N, K = dims
+    db = _grad_buffer(btargets, (N,), dy.device) if want_db else None
+    dw, db_done = None, False
+    if want_dw:
+        dw = _grad_buffer(wtargets, (N, K), dy.device)
+        db_done = fmt.gemm(dy, ldy, 1, x2, ldx, 0, dw, K, N, K, M, flags=flags, rowsum=db, **_live_kw(live, dy))
+    if want_db and not db_done:
+        d32, ld32 = fmt.f32_rows(dy, ldy, N)
+        colsum(d32, M, N, ld32, out=db)
+    return dw, db
+
+
 class LinearFn(torch.autograd.Function):
     """y = act(x W^T + b)  -- nn.Linear + optional erf-GELU / ReLU epilogue on the GEMM of `fmt` (default: fp32 rows on the fp32 MFMA GEMM, whatever
     the precision mode); act = "swish" is the plain GEMM followed by the elementwise kernel ytvln_act_fwd_* (unfused by design: one extra read and
@@ -810,37 +846,11 @@ class LinearFn(torch.autograd.Function):
             dz = fmt.empty(M, N, dy.device)
             call("ytvln_act_bwd_" + fmt.suffix, _ptr(dy), _ptr(aux), _ptr(dz), M * N, ctx.epi, _stream())
             dy = dz
-        dev = dy.device
-        dx = dw = db = None
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if want_db:
-            db = _direct_grad(ctx.btargets, (N,))
-            if db is None:
-                db = torch.empty(N, dtype=torch.float32, device=dev)
-        db_done = False
+        dx = None
         if ctx.needs_input_grad[0]:
-            w, ldw = fmt.weight(weight)
-            acc = fmt.accumulate_target(dres, M, K, dy, dy_in)
-            if acc is not None:          # dx = d(residual) + dY W, written over the residual branch's gradient
-                fmt.gemm(dy, ldy, 0, w, ldw, 0, acc, K, M, K, N, beta=1.0, flags=flags, **_rows_kw(ctx.live))
-                dx = acc.view(ctx.in_shape)
-            else:
-                dx = fmt.empty(M, K, dev)
-                fmt.gemm(dy, ldy, 0, w, ldw, 0, dx, K, M, K, N, flags=flags, **_rows_kw(ctx.live))
-                dx = dx.view(ctx.in_shape)
-                if dres is not None:
-                    dx = dx + dres.reshape(ctx.in_shape)
-                if ctx.x_was_f32:
-                    dx = dx.float()
-        if ctx.needs_input_grad[1]:
-            dw = _direct_grad(ctx.targets, (N, K))
-            if dw is None:
-                dw = torch.empty((N, K), dtype=torch.float32, device=dev)
-            # dW[N, K] = dY^T X; db = column sums of dY = row sums of the A operand (dY^T) of this launch: rides on the GEMM when it can
-            db_done = fmt.gemm(dy, ldy, 1, x2, ctx.lda, 0, dw, K, N, K, M, flags=flags, rowsum=db if want_db else None, **_live_kw(ctx.live, dy))
-        if want_db and not db_done:
-            d32, ld32 = fmt.f32_rows(dy, ldy, N)
-            colsum(d32, M, N, ld32, out=db)
+            dx = _input_grad(fmt, dy, ldy, flags, weight, (M, K, N), dres, (dy, dy_in), ctx.in_shape, ctx.live, as_f32=ctx.x_was_f32)
+        dw, db = _weight_grads(fmt, dy, ldy, flags, x2, ctx.lda, (M, N, K), ctx.targets, ctx.btargets, ctx.live,
+                               want_dw=ctx.needs_input_grad[1], want_db=ctx.has_bias and ctx.needs_input_grad[2])
         return (dx, dw, db) + tail
 
 
@@ -906,43 +916,17 @@ class FFNFn(torch.autograd.Function):
         dy, ldy, _ = fmt.grad_rows(dy, M, N)
         dev = dy.device
         dz = fmt.empty(M, I, dev)
-        db2 = _direct_grad(ctx.targets[3], (N,))
-        if db2 is None:
-            db2 = torch.empty(N, dtype=torch.float32, device=dev)
-        db1 = _direct_grad(ctx.targets[2], (I,))
-        if db1 is None:
-            db1 = torch.empty(I, dtype=torch.float32, device=dev)
         fmt.gemm(dy, ldy, 0, *fmt.weight(w2), 0, dz, I, M, I, N, aux=z, ldaux=I, epi=EPI_MUL_DGELU, **_rows_kw(ctx.live))   # dH * gelu'(z)
-        dw2 = _direct_grad(ctx.targets[1], (N, I))
-        if dw2 is None:
-            dw2 = torch.empty((N, I), dtype=torch.float32, device=dev)
         if h is None:          # recompute_h: h = gelu(z), alive for the one GEMM that reads it
             h = fmt.empty(M, I, dev)
             call("ytvln_gelu_fwd_f32", _ptr(z), _ptr(h), M * I, _stream())
-        db2_done = fmt.gemm(dy, ldy, 1, h, I, 0, dw2, I, N, I, M, rowsum=db2, **_live_kw(ctx.live, dy))          # db2 rides on the dW2 GEMM
+        dw2, db2 = _weight_grads(fmt, dy, ldy, 0, h, I, (M, N, I), ctx.targets[1], ctx.targets[3], ctx.live)          # db2 rides on the dW2 GEMM
         del h
-        if not db2_done:
-            d32, ld32 = fmt.f32_rows(dy, ldy, N)
-            colsum(d32, M, N, ld32, out=db2)
         dx = None
-        if ctx.needs_input_grad[0]:
-            w, ldw = fmt.weight(w1)
-            acc = fmt.accumulate_target(dres, M, K, dy, dy_in)      # (dy is consumed by now, but it may be retained / hooked upstream)
-            if acc is not None:          # the residual around the FFN: accumulate into its gradient (see LinearFn)
-                fmt.gemm(dz, I, 0, w, ldw, 0, acc, K, M, K, I, beta=1.0, **_rows_kw(ctx.live))
-                dx = acc.view(ctx.in_shape)
-            else:
-                dx = fmt.empty(M, K, dev)
-                fmt.gemm(dz, I, 0, w, ldw, 0, dx, K, M, K, I, **_rows_kw(ctx.live))
-                dx = dx.view(ctx.in_shape)
-                if dres is not None:
-                    dx = dx + dres.reshape(ctx.in_shape)
-        dw1 = _direct_grad(ctx.targets[0], (I, K))
-        if dw1 is None:
-            dw1 = torch.empty((I, K), dtype=torch.float32, device=dev)
-        if not fmt.gemm(dz, I, 1, x2, ctx.lda, 0, dw1, K, I, K, M, rowsum=db1, **_live_kw(ctx.live, dz)):
-            d32, ld32 = fmt.f32_rows(dz, I, I)
-            colsum(d32, M, I, ld32, out=db1)
+        if ctx.needs_input_grad[0]:          # the residual around the FFN: accumulated into its gradient where possible (see LinearFn)
+            # (dy is consumed by now, but it may be retained / hooked upstream)
+            dx = _input_grad(fmt, dz, I, 0, w1, (M, K, I), dres, (dy, dy_in), ctx.in_shape, ctx.live)
+        dw1, db1 = _weight_grads(fmt, dz, I, 0, x2, ctx.lda, (M, I, K), ctx.targets[0], ctx.targets[2], ctx.live)
         return (dx, dw1, db1, dw2, db2) + tail
 
 

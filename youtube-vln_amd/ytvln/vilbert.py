@@ -1168,25 +1168,7 @@ class BertModel(BertPreTrainedModel):
 
         ts = ops.TwoStream
         plan_t, plan_v = self._plans(attention_mask, image_attention_mask)          # (None, None) unless skip_padding is set
-        # weight gradients over the valid rows only: one list per padding mask, built here and read by the backward of every projection of that
-        # side.  Training with gradients on and padded rows only (packed rows need no list; the pair geometries re-batch one side's rows)
-        # (GEMM_LIVE_M: the same lists carry the permutation that lets the forward and input-gradient GEMMs of the side leave the padded rows
-        #  out, and the host's guess of the count for their launch plans -- _RowsHint)
-        self.live_rows = None
-        live_m = ops._lib.option("GEMM_LIVE_M") != 0
-        if (self.wgrad_live_rows and self.training and torch.is_grad_enabled() and plan_t is None and plan_v is None and ops.get_matmul_precision() == "fp32"
-                and not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE) and (ops._lib.option("GEMM_LIVE_ROWS") != 0 or live_m)):
-            lists = tuple(None if m is None or m.numel() % 32 != 0 else ops.live_rows(m, perm=live_m) for m in (attention_mask, image_attention_mask))
-            if lists[0] is not None or lists[1] is not None:
-                self.live_rows = lists
-            if live_m:
-                if self._rows_hints is None:
-                    self._rows_hints = (_RowsHint(), _RowsHint())
-                for side, lr in enumerate(lists):
-                    if lr is not None:
-                        fixed = None if self.rows_hint is None else self.rows_hint[side]
-                        lr.forward = bool(self.forward_live_rows)
-                        lr.hint = min(lr.rows, self._rows_hints[side].step(lr.count) if fixed is None else int(fixed))
+        self.live_rows = self._live_lists((attention_mask, image_attention_mask), plan_t is not None or plan_v is not None)
         try:
             _Runtime.live = self.live_rows
             if not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE):
@@ -1244,6 +1226,27 @@ class BertModel(BertPreTrainedModel):
             zero = self.padding_overflow.new_zeros(())
             self.padding_overflow += torch.stack([zero if p is None else p.counts[1] for p in plans])
         return plans[0], plans[1]
+
+    def _live_lists(self, masks, packed: bool):
+        """(text LiveRows | None, image LiveRows | None) of this forward, or None: one list per padding mask, built here and read by the backward
+        of every projection of that side (weight gradients over the valid rows only).  Training with gradients on and padded rows only (`packed`
+        rows need no list; the pair geometries re-batch one side's rows).  GEMM_LIVE_M: the same lists carry the permutation that lets the
+        forward and input-gradient GEMMs of the side leave the padded rows out, and the host's guess of the count for their launch plans
+        (_RowsHint)."""
+        live_m = ops._lib.option("GEMM_LIVE_M") != 0
+        if not (self.wgrad_live_rows and self.training and torch.is_grad_enabled() and not packed and ops.get_matmul_precision() == "fp32"
+                and not (self.encoder.in_batch_pairs or self.encoder.FAST_MODE) and (ops._lib.option("GEMM_LIVE_ROWS") != 0 or live_m)):
+            return None
+        lists = tuple(None if m is None or m.numel() % 32 != 0 else ops.live_rows(m, perm=live_m) for m in masks)
+        if live_m:
+            if self._rows_hints is None:
+                self._rows_hints = (_RowsHint(), _RowsHint())
+            for side, lr in enumerate(lists):
+                if lr is not None:
+                    fixed = None if self.rows_hint is None else self.rows_hint[side]
+                    lr.forward = bool(self.forward_live_rows)
+                    lr.hint = min(lr.rows, self._rows_hints[side].step(lr.count) if fixed is None else int(fixed))
+        return lists if (lists[0] is not None or lists[1] is not None) else None
 
 
 class BertForMultiModalPreTraining(BertPreTrainedModel):
