@@ -314,6 +314,58 @@ int ytvln_expand_records_f32(const float* pool_features,   /* [pool_rows, F]    
                              int64_t* bad,                 /* NULL or [1], accumulates */
                              void* stream);
 
+/* The two expansions with the region masking of ytvln_randomize_regions and the bf16 rounding of ytvln_cast_f32_bf16 in the SAME launch
+ * (csrc/pool.hip): the MVM targets are written once, the features once in the type the model reads, and the padded probabilities are never
+ * materialised.  For padded row r = slot * boxes + j, let (feature row, probs row, box columns, m) be what ytvln_expand_ragged_f32 /
+ * ytvln_expand_records_f32 write for that row from the same pool, index and view -- same bad-slot rules (an EMPTY record frame is bad), same
+ * order of the range checks, same `bad` counter, same column 11.  Then
+ *   draw = p[r] when `p` is given, else u01(x word of the Philox block r of (rng, site)) when `rng` is given: the draw
+ *          ytvln_randomize_regions takes for flat row r of the same (rng, site);            q = draw * (float)m
+ *   sel  = q >= (float)0.85:   out_targets[r, :] = sel ? probs row : 1.0f / (float)C,   out_targets_mask[r] = sel
+ *          (the global region of a record slot holds (float)(1.0 / C) when selected)
+ *   zero = q >= (float)(0.85 + 0.15 * 0.1):   out_features[r, :] = zero ? exact zeros : feature row
+ *   out_boxes and out_masks are the unmasked ones.
+ * `p` and `rng` both NULL: masking is off -- features unmasked; out_targets / out_targets_mask, when given, hold 1.0f / (float)C and 0 (what
+ *   mask_batch(masked_vision=False) makes of the unfused expansion), and pool_probs, out_targets and out_targets_mask may all be NULL
+ *   (inference re-ranking: bf16 features, no probabilities).  Pool probabilities are read for the rows with sel only.
+ * feature_dtype = YTVLN_DT_F32: out_features is float [slots * boxes, F].  YTVLN_DT_BF16: uint16_t [slots * boxes, F] (2-byte aligned, F may
+ *   be odd), every value rounded once to nearest even with the conversion of ytvln_cast_f32_bf16; zeros stay zeros.  Everything else stays
+ *   fp32 / int64.
+ * Every output element is written exactly once whatever the outputs held on entry.  No allocation, no host synchronisation, no atomics but
+ * the `bad` counter; capturable.  The bad arguments of the unfused entry points, an unknown feature_dtype, masking without pool_probs,
+ * out_targets or out_targets_mask, only one of out_targets / out_targets_mask, or targets with C <= 0 return a negative code and launch
+ * nothing. */
+int ytvln_expand_ragged_masked(const float* pool_features,   /* [pool_rows, F]                                   */
+                               const float* pool_loc,        /* [pool_rows, L], L <= 11                          */
+                               const float* pool_probs,      /* [pool_rows, C], or NULL with masking off         */
+                               const int64_t* offsets,       /* [pool_frames + 1]                                */
+                               int64_t pool_frames, int64_t pool_rows,
+                               const int64_t* index,         /* [slots], -1 = padding                            */
+                               int64_t slots, int frames, int boxes, int F, int L, int C,
+                               const float* p,               /* [slots * boxes] explicit draws, or NULL          */
+                               const int64_t* rng,           /* (seed, counter) on the device, or NULL           */
+                               int64_t site,
+                               void* out_features,           /* [slots * boxes, F] of feature_dtype              */
+                               int feature_dtype,            /* YTVLN_DT_F32 | YTVLN_DT_BF16                     */
+                               float* out_boxes,             /* [slots * boxes, 12]                              */
+                               float* out_targets,           /* [slots * boxes, C], or NULL with masking off     */
+                               int64_t* out_masks,           /* [slots * boxes]                                  */
+                               int64_t* out_targets_mask,    /* [slots * boxes], together with out_targets       */
+                               int64_t* bad,                 /* NULL or [1], accumulates                         */
+                               void* stream);
+int ytvln_expand_records_masked(const float* pool_features,   /* [pool_rows, F]                                   */
+                                const float* pool_geom,       /* [pool_rows, 8]                                   */
+                                const float* pool_probs,      /* [pool_rows, C], or NULL with masking off         */
+                                const float* pool_global,     /* [pool_frames, F] from ytvln_pool_global_rows_f32 */
+                                const int64_t* offsets,       /* [pool_frames + 1]                                */
+                                int64_t pool_frames, int64_t pool_rows,
+                                const int64_t* index,         /* [slots], -1 = padding                            */
+                                const double* view,           /* [slots, 2] heading, next heading, or NULL        */
+                                int64_t slots, int frames, int boxes, int F, int C,
+                                const float* p, const int64_t* rng, int64_t site,
+                                void* out_features, int feature_dtype, float* out_boxes, float* out_targets, int64_t* out_masks,
+                                int64_t* out_targets_mask, int64_t* bad, void* stream);
+
 /* out[j, :] = x[idx[j], :] (zeros where idx[j] < 0): row gather in front of the loss-aware prediction heads (only rows that
  * carry a masked-language / masked-vision target are decoded; "next" row of SURVEY.md section 8f).  Backward =
  * ytvln_scatter_add_rows_f32 with skip_idx = -1. */

@@ -8,14 +8,10 @@
 
 namespace ytvln {
 
-// float thresholds exactly as torch compares an fp32 tensor with the reference's Python doubles (scalar -> fp32)
-__device__ __forceinline__ float thr_mask() { return (float)0.85; }
+// float thresholds exactly as torch compares an fp32 tensor with the reference's Python doubles (scalar -> fp32); thr_mask, thr_reg_zero and
+// the uniform draw u01 are in common.h (pool.hip masks regions with them too)
 __device__ __forceinline__ float thr_tok_random() { return (float)(0.85 + 0.15 * 0.8); }
 __device__ __forceinline__ float thr_tok_keep() { return (float)(0.85 + 0.15 * 0.9); }
-__device__ __forceinline__ float thr_reg_zero() { return (float)(0.85 + 0.15 * 0.1); }
-
-// uniform in [0, 1) with 24 random bits (torch.rand's fp32 construction)
-__device__ __forceinline__ float u01(uint32_t bits) { return (float)(bits >> 8) * (1.0f / 16777216.0f); }
 
 // randomize_tokens (common.py:213-270 with mask_action_rate == 0; randomize_tokens_action_kernel below is the other case):  p = U * mask;  p >= 0.85 -> target = token, token = [MASK];
 // p >= 0.97 -> token = random id;  p >= 0.985 -> token = original.  targets = -1 elsewhere.

@@ -104,6 +104,20 @@ __device__ __forceinline__ float drop_scale1(const DropKey& k, uint64_t e, uint3
     return sel >= thr ? inv_keep : 0.0f;
 }
 
+// uniform in [0, 1) with 24 random bits (torch.rand's fp32 construction)
+__device__ __forceinline__ float u01(uint32_t bits) { return (float)(bits >> 8) * (1.0f / 16777216.0f); }
+
+// float thresholds of the BERT / ViLBERT masking exactly as torch compares an fp32 tensor with the reference's Python doubles (scalar -> fp32);
+// shared by the masking kernels (batch.hip) and the frame-pool expansion that masks regions in the same launch (pool.hip)
+__device__ __forceinline__ float thr_mask() { return (float)0.85; }
+__device__ __forceinline__ float thr_reg_zero() { return (float)(0.85 + 0.15 * 0.1); }
+
+// fp32 -> bf16 bits, the one conversion of the library's bf16 writers that go through it (cast_f32_bf16_kernel, the bf16 GEMM epilogues, the
+// bf16 feature output of the frame pools)
+__device__ __forceinline__ uint32_t f2bf(float f) {          // round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32 semantics)
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+}
+
 // Cheap per-element keep decision for attention-probability dropout: one 32-bit hash per score, the same in every fragment layout (the forward
 // / dQ kernels hold 4 consecutive keys per lane, the dK/dV kernel 4 consecutive queries).  The element index enters through two odd multipliers
 // (lo * C1 is an add per element for the kernels: lo advances by compile-time steps), the site / step key -- itself put through a full avalanche

@@ -56,9 +56,7 @@ struct BfArgs {
 constexpr int KT = 64;           // k-tile depth in bf16 elements
 
 __device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
-__device__ __forceinline__ uint32_t f2bf(float f) {          // round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32 semantics)
-    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
-}
+// (f2bf, the rounding the other way: common.h)
 
 template <typename CT> struct Elem;
 template <> struct Elem<float> {

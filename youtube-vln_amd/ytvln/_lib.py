@@ -67,6 +67,9 @@ SIGNATURES = {
     "ytvln_expand_ragged_f32": [P, P, P, P, I64, I64, P, I64, I32, I32, I32, I32, I32, P, P, P, P, P, P],
     "ytvln_pool_global_rows_f32": [P, P, I64, I64, I32, P, P],
     "ytvln_expand_records_f32": [P, P, P, P, P, I64, I64, P, P, I64, I32, I32, I32, I32, P, P, P, P, P, P],
+    # the two expansions with region masking and the bf16 feature output in the same launch
+    "ytvln_expand_ragged_masked": [P, P, P, P, I64, I64, P, I64, I32, I32, I32, I32, I32, P, P, I64, P, I32, P, P, P, P, P, P],
+    "ytvln_expand_records_masked": [P, P, P, P, P, I64, I64, P, P, I64, I32, I32, I32, I32, P, P, I64, P, I32, P, P, P, P, P, P],
     "ytvln_attn_keep_bytes": [I32, I32, I32, I32],
     "ytvln_attn_fwd_bf16": [P, P, I32, I32, I32, F32, P, P],
     "ytvln_attn_bwd_bf16": [P, P, I32, I32, I32, F32, P, P],

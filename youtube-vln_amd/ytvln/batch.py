@@ -12,6 +12,8 @@ sits in HBM.  The loader then only has to ship the un-masked tokens / features /
     global_rows(pool_features, offsets)              -> the readers' global (mean) feature row of every pool frame, numpy's summation order
     expand_records(pool..., offsets, index, boxes)   -> expand_ragged from RAW records: global region, box geometry, headings on the device
     RecordPool(capacity_rows, capacity_frames)       pinned staging + static device buffers around global_rows + expand_records
+    expand_ragged_masked / expand_records_masked     the expansions with randomize_regions, and bf16 features on request, in the same launch
+    pool.expand_masked(index, boxes, ...)            -> items 1, 2, 4, 3, 5; then mask_batch(..., vision_premasked=True) for the tokens
 
 Draws come from the library's Philox stream (`ops.DropoutState`: seed + device-side counter, so the masks change every call and
 replay inside a hipGraph); passing `p=` / `random_tokens=` (/ `action_choice=`) reproduces the reference functions bit for bit (tests).
@@ -32,7 +34,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from ._lib import call
+from ._lib import DT_BF16, DT_F32, call
 
 MASK_TOKEN_ID = 103         # tokenizer.vocab["[MASK]"] of bert-base-uncased (common.py:255)
 VOCAB_SIZE = 30522          # len(tokenizer.vocab)
@@ -320,6 +322,118 @@ def expand_records(pool_features: Tensor, pool_geom: Tensor, pool_probs: Optiona
     return f, bx, pr, m
 
 
+_FEATURE_DTYPES = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
+
+
+def _check_masked(who: str, inputs, out, bad, lead, F: int, C: int, masked_vision: bool, p, feature_dtype):
+    """`_check_out` for the masked expansions: `feature_dtype`, `p` and the five tensors of `out` (ValueError), then every tensor on the GPU
+    (RuntimeError) and on one device.  Returns (image_features, image_boxes, image_targets, image_masks, image_targets_mask), allocated here
+    when `out` is None; targets and targets mask are None when there are no `pool_probs` (masking off)."""
+    if feature_dtype not in _FEATURE_DTYPES:
+        raise ValueError(f"ytvln.batch: `feature_dtype` must be torch.float32 or torch.bfloat16, got {feature_dtype!r}")
+    probs = dict(inputs)["pool_probs"] is not None
+    if masked_vision and not probs:
+        raise ValueError("ytvln.batch: masked_vision needs `pool_probs` (the targets of a selected region are its class probabilities)")
+    if p is not None:
+        if not masked_vision:
+            raise ValueError("ytvln.batch: explicit draws `p` go with masked_vision=True")
+        _want(p, "p", torch.float32, lead)
+    if out is not None:
+        if len(out) != 5:
+            raise ValueError("ytvln.batch: `out` is (image_features, image_boxes, image_targets, image_masks, image_targets_mask)")
+        f, bx, tg, m, tm = out
+        _want(f, "out[0]", feature_dtype, (*lead, F))
+        _want(bx, "out[1]", torch.float32, (*lead, 12))
+        if (tg is None) == probs or (tm is None) == probs:
+            raise ValueError("ytvln.batch: out[2] (image_targets), out[4] (image_targets_mask) and `pool_probs` go together: all given or all None")
+        if tg is not None:
+            _want(tg, "out[2]", torch.float32, (*lead, C))
+            _want(tm, "out[4]", torch.int64, lead)
+        _want(m, "out[3]", torch.int64, lead)
+    if bad is not None:
+        _want(bad, "bad", torch.int64, (1,))
+    tensors = list(inputs) + [("p", p), ("bad", bad)] + ([(f"out[{i}]", t) for i, t in enumerate(out)] if out is not None else [])
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"ytvln.batch: `{name}` must live on the GPU (no CPU path)")
+    dev = inputs[0][1].device
+    if any(t is not None and t.device != dev for _, t in tensors):
+        raise ValueError(f"ytvln.batch: {who} needs all its tensors on one device")
+    if out is None:
+        f = torch.empty(*lead, F, dtype=feature_dtype, device=dev)
+        bx = torch.empty(*lead, 12, dtype=torch.float32, device=dev)
+        tg = torch.empty(*lead, C, dtype=torch.float32, device=dev) if probs else None
+        m = torch.empty(*lead, dtype=torch.int64, device=dev)
+        tm = torch.empty(*lead, dtype=torch.int64, device=dev) if probs else None
+    return f, bx, tg, m, tm
+
+
+def _draws(masked_vision: bool, p, device):
+    """(p pointer, rng pointer, site, the DropoutState to keep alive) of a masked expansion: the explicit draws, or the next site of the
+    device's Philox stream exactly as `randomize_regions` takes it, or nothing (masking off)."""
+    if not masked_vision:
+        return None, None, 0, None
+    if p is not None:
+        return ops._ptr(p), None, 0, None
+    st = ops.DropoutState(device)
+    return None, ops._ptr(st.tensor), st.next_site(), st
+
+
+def expand_ragged_masked(pool_features: Tensor, pool_locations: Tensor, pool_probs: Optional[Tensor], offsets: Tensor, index: Tensor, boxes: int,
+                         masked_vision: bool = True, p: Optional[Tensor] = None, feature_dtype=torch.float32,
+                         out: Optional[Sequence[Optional[Tensor]]] = None, bad: Optional[Tensor] = None):
+    """`expand_ragged` + `randomize_regions` (+ the bf16 rounding of the features the bf16-resident model applies) in ONE launch
+    (`ytvln_expand_ragged_masked`): the MVM targets are written once, the features once in `feature_dtype` (torch.float32 or torch.bfloat16,
+    each value rounded once to nearest even), and the padded class probabilities are never materialised.  Returns (image_features
+    [bs, K, frames*boxes, F], image_boxes [.., 12], image_targets [.., C], image_masks [..] int64, image_targets_mask [..] int64): bit for bit
+    what `expand_ragged` followed by `randomize_regions(features, probs, masks)` -- and `.to(torch.bfloat16)` -- gives, features in place
+    included; drop them into entries 1, 2, 4, 3, 5 of the 16-tuple and call `mask_batch(..., vision_premasked=True)`.
+
+    `p` (fp32 [bs, K, frames*boxes]) supplies the draws as it does for `randomize_regions`; without it the device's Philox stream
+    (`ops.DropoutState`) supplies them exactly as for that function.  `masked_vision=False`: features unmasked, targets 1/C and a zero
+    targets mask -- what `mask_batch(masked_vision=False)` returns; `pool_probs` may then be None, and targets and targets mask come back None
+    (inference re-ranking: bf16 features, no probabilities).  `out` = the five tensors (the static inputs of a captured step; the two target
+    entries None together with `pool_probs`); `bad` as for `expand_ragged`.  Shapes and dtypes are checked first (ValueError, nothing
+    touched); there is no CPU path."""
+    boxes, rows, F, C, (bs, K, frames) = _check_pool(boxes, pool_features, [("pool_locations", pool_locations, None)], pool_probs, offsets, index)
+    L = pool_locations.shape[1]
+    if L > 11:
+        raise ValueError(f"ytvln.batch: `pool_locations` has {L} columns; the boxes hold 11 next to the position column")
+    masked_vision = bool(masked_vision)
+    f, bx, tg, m, tm = _check_masked("expand_ragged_masked", [("pool_features", pool_features), ("pool_locations", pool_locations),
+                                                              ("pool_probs", pool_probs), ("offsets", offsets), ("index", index)],
+                                     out, bad, (bs, K, frames * boxes), F, C, masked_vision, p, feature_dtype)
+    p_ptr, rng_ptr, site, _keep = _draws(masked_vision, p, pool_features.device)
+    call("ytvln_expand_ragged_masked", ops._ptr(pool_features), ops._ptr(pool_locations), ops._ptr(pool_probs), ops._ptr(offsets),
+         offsets.numel() - 1, rows, ops._ptr(index), bs * K * frames, frames, boxes, F, L, C, p_ptr, rng_ptr, site, f.data_ptr(),
+         _FEATURE_DTYPES[feature_dtype], ops._ptr(bx), ops._ptr(tg), ops._ptr(m), ops._ptr(tm), ops._ptr(bad), ops._stream())
+    return f, bx, tg, m, tm
+
+
+def expand_records_masked(pool_features: Tensor, pool_geom: Tensor, pool_probs: Optional[Tensor], pool_global: Tensor, offsets: Tensor,
+                          index: Tensor, boxes: int, view: Optional[Tensor] = None, masked_vision: bool = True, p: Optional[Tensor] = None,
+                          feature_dtype=torch.float32, out: Optional[Sequence[Optional[Tensor]]] = None, bad: Optional[Tensor] = None):
+    """`expand_ragged_masked` for a pool of RAW records (`ytvln_expand_records_masked`): `expand_records` + `randomize_regions` (+ the bf16
+    rounding) in one launch, same five outputs, same `masked_vision` / `p` / `feature_dtype` / `out` / `bad`.  The global region of a slot
+    (row 0) is a region like any other: selected, its targets are its uniform distribution; zeroed, its feature row is zeros."""
+    boxes, rows, F, C, (bs, K, frames) = _check_pool(boxes, pool_features, [("pool_geom", pool_geom, 8)], pool_probs, offsets, index)
+    _want(pool_global, "pool_global", torch.float32, (offsets.numel() - 1, F))
+    if view is not None:
+        _want(view, "view", torch.float64, (bs, K, frames, 2))
+    if pool_probs is not None and C == 0:
+        raise ValueError("ytvln.batch: `pool_probs` needs at least one class (the global region holds 1 / C)")
+    masked_vision = bool(masked_vision)
+    f, bx, tg, m, tm = _check_masked("expand_records_masked", [("pool_features", pool_features), ("pool_geom", pool_geom),
+                                                               ("pool_probs", pool_probs), ("pool_global", pool_global), ("offsets", offsets),
+                                                               ("index", index), ("view", view)],
+                                     out, bad, (bs, K, frames * boxes), F, C, masked_vision, p, feature_dtype)
+    p_ptr, rng_ptr, site, _keep = _draws(masked_vision, p, pool_features.device)
+    call("ytvln_expand_records_masked", ops._ptr(pool_features), ops._ptr(pool_geom), ops._ptr(pool_probs), ops._ptr(pool_global),
+         ops._ptr(offsets), offsets.numel() - 1, rows, ops._ptr(index), ops._ptr(view), bs * K * frames, frames, boxes, F, C, p_ptr, rng_ptr, site,
+         f.data_ptr(), _FEATURE_DTYPES[feature_dtype], ops._ptr(bx), ops._ptr(tg), ops._ptr(m), ops._ptr(tm), ops._ptr(bad), ops._stream())
+    return f, bx, tg, m, tm
+
+
 class _FramePool:
     """What RaggedPool and RecordPool share: per-row fp32 buffers `host_<name>` (pinned staging) / `<name>` (static device buffer) for every
     (name, columns) of `_columns`, `offsets`, `bad`, keys -> ids, `index`, `upload` and `reset`.  The subclasses say which arrays a frame
@@ -474,6 +588,15 @@ class RaggedPool(_FramePool):
             index = index.to(self.device, non_blocking=True)
         return expand_ragged(self.features, self.locations, self.probs, self.offsets, index, boxes, out=out, bad=self.bad)
 
+    def expand_masked(self, index: Tensor, boxes: int, masked_vision: bool = True, feature_dtype=torch.float32, out=None):
+        """`expand_ragged_masked` on the device buffers (a CPU `index` is uploaded first): `expand` with the region masking, and the bf16
+        rounding of the features when asked for, in the same launch.  The draws are the device's Philox stream's."""
+        self._need_device("expand_masked")
+        if torch.is_tensor(index) and not index.is_cuda:
+            index = index.to(self.device, non_blocking=True)
+        return expand_ragged_masked(self.features, self.locations, self.probs, self.offsets, index, boxes, masked_vision=masked_vision,
+                                    feature_dtype=feature_dtype, out=out, bad=self.bad)
+
 
 class RecordPool(_FramePool):
     """RaggedPool for RAW records: the frames of one step as they come off the disk (`reader.records(query)` / `reader.record(key)`:
@@ -523,9 +646,22 @@ class RecordPool(_FramePool):
         return expand_records(self.features, self.geom, self.probs, self.global_features, self.offsets, index, boxes, view=view, out=out,
                               bad=self.bad)
 
+    def expand_masked(self, index: Tensor, boxes: int, view: Optional[Tensor] = None, masked_vision: bool = True, feature_dtype=torch.float32,
+                      out=None):
+        """`global_rows` + `expand_records_masked` on the device buffers (a CPU `index` or `view` is uploaded first): `expand` with the region
+        masking, and the bf16 rounding of the features when asked for, in the expansion's launch."""
+        self._need_device("expand_masked")
+        if torch.is_tensor(index) and not index.is_cuda:
+            index = index.to(self.device, non_blocking=True)
+        if torch.is_tensor(view) and not view.is_cuda:
+            view = view.to(self.device, non_blocking=True)
+        global_rows(self.features, self.offsets, out=self.global_features)
+        return expand_records_masked(self.features, self.geom, self.probs, self.global_features, self.offsets, index, boxes, view=view,
+                                     masked_vision=masked_vision, feature_dtype=feature_dtype, out=out, bad=self.bad)
+
 
 def mask_batch(batch: Sequence[Tensor], vocab_size: int = VOCAB_SIZE, mask_token_id: int = MASK_TOKEN_ID, masked_language: bool = True,
-               masked_vision: bool = True, mask_action_rate: float = 0.0, args=None) -> List[Tensor]:
+               masked_vision: bool = True, mask_action_rate: float = 0.0, args=None, vision_premasked: bool = False) -> List[Tensor]:
     """Apply both maskings to an un-masked device batch in the 16-tuple layout of `get_model_input` (utils/utils_init.py:34-53):
     1 image_features, 3 image_masks, 4 image_targets (class probabilities in, MVM targets out), 5 image_targets_mask (out),
     6 instr_tokens [bs, K, T], 7 instr_mask, 8 instr_targets (out).
@@ -533,7 +669,10 @@ def mask_batch(batch: Sequence[Tensor], vocab_size: int = VOCAB_SIZE, mask_token
     `masked_language` / `masked_vision` / `mask_action_rate` are the reference's options of the same names; `args` (the parsed command
     line) supplies all three when given.  A disabled masking returns what the reference's dataset returns (`all_dataset.py:251-261`):
     instr_targets = -1, or image_targets = 1/C with a zero image_targets_mask, and the inputs untouched.  The action draw is per
-    dataset item, i.e. per row of the batch dimension: all K instructions of an item together, like the reference."""
+    dataset item, i.e. per row of the batch dimension: all K instructions of an item together, like the reference.
+
+    `vision_premasked=True`: entries 1, 4 and 5 already are what the vision masking produces (a pool's `expand_masked` wrote them) and are
+    left exactly as they came, whatever `masked_vision` says; the token side works as before."""
     if args is not None:
         masked_language = bool(getattr(args, "masked_language", masked_language))
         masked_vision = bool(getattr(args, "masked_vision", masked_vision))
@@ -544,7 +683,9 @@ def mask_batch(batch: Sequence[Tensor], vocab_size: int = VOCAB_SIZE, mask_token
         b[6], b[8] = randomize_tokens(b[6], b[7], vocab_size, mask_token_id, mask_action_rate=rate)
     else:
         b[8] = torch.full_like(b[6], -1)
-    if masked_vision:
+    if vision_premasked:
+        pass                            # entries 1, 4, 5 stay the objects the pool's expand_masked wrote
+    elif masked_vision:
         b[1], b[4], b[5] = randomize_regions(b[1], b[4], b[3])
     else:
         b[4], b[5] = torch.ones_like(b[4]) / b[4].shape[-1], torch.zeros_like(b[3])

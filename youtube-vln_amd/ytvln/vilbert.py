@@ -1064,6 +1064,14 @@ class BertPreTrainedModel(nn.Module):
         return model
 
 
+def _stays_bf16(x, rows: int, weight) -> bool:
+    """Region features that arrive as bf16 (a frame pool's `expand_masked(feature_dtype=torch.bfloat16)`) enter the feature projection as they
+    are when that projection, fed `rows` fp32 rows, would have rounded them to bf16 itself (`ops._bf16_eligible`): bf16 -> fp32 -> bf16 is the
+    identity, so the outputs are bit for bit those of the converted input, with one cast launch fewer.  Anything else is converted to fp32."""
+    return (x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0
+            and ops._bf16_eligible(rows, weight.shape[0], x.shape[-1]))
+
+
 class BertImageEmbeddings(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -1076,7 +1084,8 @@ class BertImageEmbeddings(nn.Module):
         self.dropout = nn.Dropout(config.hidden_dropout_prob)
 
     def forward(self, input_ids, input_loc):
-        if input_ids.dtype != torch.float32:
+        if input_ids.dtype != torch.float32 and not _stays_bf16(input_ids, input_ids.numel() // max(input_ids.shape[-1], 1),
+                                                                self.image_embeddings.weight):
             input_ids = input_ids.float()
         if input_loc.dtype != torch.float32:
             input_loc = input_loc.float()
@@ -1185,7 +1194,9 @@ class BertModel(BertPreTrainedModel):
                 if plan_t is not None:
                     embedding_output = ops.rows_pack(embedding_output, plan_t).view(1, plan_t.capacity, -1)
             if plan_v is not None:          # the 2048-wide feature projection and the fused embedding run on packed rows (bf16 mode: packed, then cast)
-                input_imgs = ops.rows_pack(input_imgs if input_imgs.dtype == torch.float32 else input_imgs.float(), plan_v).unsqueeze(0)
+                if input_imgs.dtype != torch.float32 and not _stays_bf16(input_imgs, plan_v.capacity, self.v_embeddings.image_embeddings.weight):
+                    input_imgs = input_imgs.float()          # (bf16 features the projection would round anyway are packed as bf16 rows)
+                input_imgs = ops.rows_pack(input_imgs, plan_v).unsqueeze(0)
                 image_loc = ops.rows_pack(image_loc if image_loc.dtype == torch.float32 else image_loc.float(), plan_v).unsqueeze(0)
             with _live(1):
                 v_embedding_output = self.v_embeddings(input_imgs, image_loc)
