@@ -42,9 +42,10 @@ def heads_of(x, N, T, heads, d):
     return x.double().reshape(N, T, heads, d).permute(0, 2, 1, 3)
 
 
-def scores(q, k, mask, bias, scale, emulate):
-    """s[N, heads, Tq, Tk] = q.k * scale + mask (+ bias); mask [N, Tk] or None, bias dense [N, heads, Tq, Tk] or None (may hold -inf)"""
-    s = q @ k.transpose(-1, -2)
+def scores(q, k, mask, bias, scale, emulate, qk=None):
+    """s[N, heads, Tq, Tk] = q.k * scale + mask (+ bias); mask [N, Tk] or None, bias dense [N, heads, Tq, Tk] or None (may hold -inf).
+    qk: the contraction q.k where the caller has its own (tests/attn_f32_ref.py: summed in fp32); None = the fp64 product."""
+    s = q @ k.transpose(-1, -2) if qk is None else qk
     if not emulate:
         s = s * scale
         if mask is not None:
@@ -229,11 +230,10 @@ def make_mask(N, Tk, pattern):
     return mask
 
 
-def packed_inputs(N, heads, d, Tq, Tk, seed=1):
-    """A [N*Tq, 3H], B [N*Tk, 3H], dout [N*Tq, H] in bf16; q = block Q_OFF of A, k / v = blocks K_OFF / V_OFF of B"""
+def packed_inputs(N, heads, d, Tq, Tk, seed=1, dtype=torch.bfloat16):
+    """A [N*Tq, 3H], B [N*Tk, 3H], dout [N*Tq, H] in bf16 (or `dtype`); q = block Q_OFF of A, k / v = blocks K_OFF / V_OFF of B"""
     H = heads * d
-    bf = torch.bfloat16
-    return rnd((N * Tq, 3 * H), seed).to(bf), rnd((N * Tk, 3 * H), seed + 1).to(bf), rnd((N * Tq, H), seed + 2).to(bf)
+    return rnd((N * Tq, 3 * H), seed).to(dtype), rnd((N * Tk, 3 * H), seed + 1).to(dtype), rnd((N * Tq, H), seed + 2).to(dtype)
 
 
 def packed_views(A, B, dout, N, heads, d, Tq, Tk):
@@ -245,12 +245,12 @@ def packed_views(A, B, dout, N, heads, d, Tq, Tk):
 RISING_C = (0.0, 1.0, 1.3, 1.6, 2.6)          # the key tiles' levels c_j: steps of 1, 0.3, 0.3, 1
 
 
-def rising_inputs(d, N=2, heads=2, Tq=64, Tk=160, seed=5):
+def rising_inputs(d, N=2, heads=2, Tq=64, Tk=160, seed=5, dtype=torch.bfloat16):
     """Scores a_i * c_j from q and k that are multiples of one vector u (|u|^2 = sqrt(d), so scale q.k = a_i c_j before the bf16 rounding of q
     and k).  c_j is RISING_C by key tile (+ 0.02 N(0,1)).  a_i: query block 0 spreads -15 .. 35 (shuffled) -- rows with a > 12 move the wave's
     reference at the steps of 1 and after the two steps of 0.3 together (a * 0.6 > 12 needs a > 20), the rows between are stale there, rows with
     a < 0 have their maximum in the first tile; query block 1 spreads -3 .. 3 and never moves its reference after the first tile (3 * 2.6 < 12).
-    Head 1 uses 0.7 a.  -> separate bf16 q, k, v, dout as [N*T, H] rows."""
+    Head 1 uses 0.7 a.  -> separate bf16 (or `dtype`) q, k, v, dout as [N*T, H] rows."""
     g = torch.Generator().manual_seed(seed)
     H = heads * d
     u = torch.randn(d, generator=g)
@@ -260,20 +260,18 @@ def rising_inputs(d, N=2, heads=2, Tq=64, Tk=160, seed=5):
     hs = torch.tensor([1.0, 0.7] * heads)[:heads]
     q = (a[None, :, None, None] * hs[None, None, :, None] * u).expand(N, Tq, heads, d).reshape(N * Tq, H)
     k = (c[None, :, None, None] * u).expand(N, Tk, heads, d).reshape(N * Tk, H)
-    bf = torch.bfloat16
-    return q.to(bf), k.to(bf), rnd((N * Tk, H), seed + 1).to(bf), rnd((N * Tq, H), seed + 2).to(bf)
+    return q.to(dtype), k.to(dtype), rnd((N * Tk, H), seed + 1).to(dtype), rnd((N * Tq, H), seed + 2).to(dtype)
 
 
-def pair_inputs(N, R, T, heads, d, seed=11):
-    """BertBiAttention's operands in bf16: q1 [N*R, Hb], kv1 [N*R, 2Hb], q2 [N*T, Hb], kv2 [N*T, 2Hb], masks over regions / tokens with padded
+def pair_inputs(N, R, T, heads, d, seed=11, dtype=torch.bfloat16):
+    """BertBiAttention's operands in bf16 (or `dtype`): q1 [N*R, Hb], kv1 [N*R, 2Hb], q2 [N*T, Hb], kv2 [N*T, 2Hb], masks over regions / tokens with padded
     tails on different pairs, and the two context gradients g1 [N*T, Hb], g2 [N*R, Hb]."""
     Hb = heads * d
-    bf = torch.bfloat16
-    q1, kv1, q2, kv2 = (rnd((N * n_, w * Hb), seed + i).to(bf) for i, (n_, w) in enumerate(((R, 1), (R, 2), (T, 1), (T, 2))))
+    q1, kv1, q2, kv2 = (rnd((N * n_, w * Hb), seed + i).to(dtype) for i, (n_, w) in enumerate(((R, 1), (R, 2), (T, 1), (T, 2))))
     m1, m2 = torch.zeros(N, R), torch.zeros(N, T)
     m1[1, R - 9:] = -10000.0
     m2[0, T - 5:] = -10000.0
-    return q1, kv1, q2, kv2, m1, m2, rnd((N * T, Hb), 91).to(bf), rnd((N * R, Hb), 92).to(bf)
+    return q1, kv1, q2, kv2, m1, m2, rnd((N * T, Hb), 91).to(dtype), rnd((N * R, Hb), 92).to(dtype)
 
 
 def with_inf_column(bias):

@@ -1,5 +1,7 @@
-"""The alternative forms of the fp32 attention kernels against each other -- a second net under the direct fp64 tests of
-tests/test_kernels_gpu.py (test_attention_fwd_bwd / test_attention_dropout run every form, the one-wave dK/dV kernel included, against fp64).
+"""The alternative forms of the fp32 attention kernels against each other -- a second net under the direct fp64 tests.  Every form, the
+one-wave dK/dV kernel and the stored-dS backward included, runs against fp64 per row and per 32-row block in tests/test_attn_f32_rows_gpu.py
+(its `form` fixture: five settings of the options); test_attention_fwd_bwd / test_attention_dropout of tests/test_kernels_gpu.py hold whole
+tensors, one relative L2 each, under three.
 
 The one-wave-per-SIMD kernels (attention.hip: attn_fwd_w1_body, attn_bwd_dq_w1_body, attn_bwd_dkv_w1_body) replace the two-wave / wave-pair
 kernels for launches that meet their conditions (unpadded d = 128 / d = 64 heads, fp32 operands; dK/dV: at least two rounds of wave slots).

@@ -60,8 +60,13 @@ struct AttnArgs {
 __device__ __forceinline__ int krow(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // scaled + masked score with the reference's two roundings (scores / sqrt(d), then + mask; vilbert.py:295-297): the
-// additive mask is -10000, so an fma here would change fully-masked rows at the 1e-3 level.
-__device__ __forceinline__ float score(float s, float scale, float mask) { return __fadd_rn(__fmul_rn(s, scale), mask); }
+// additive mask is -10000, so an fma here would change fully-masked rows at the 1e-3 level.  Contraction is switched off by name: __fmul_rn /
+// __fadd_rn are plain `*` / `+` in the HIP headers, which hipcc (fp-contract=fast) fused into ONE v_fmac_f32 -- a single rounding.
+__device__ __forceinline__ float score(float s, float scale, float mask) {
+#pragma clang fp contract(off)
+    const float scaled = s * scale;
+    return scaled + mask;
+}
 
 // ---- LDS tile streaming ------------------------------------------------------------------------------------------------
 // A 32 x DP tile lives in LDS as S[row][DP] with the 16-byte granule g of row r stored at position g ^ (r & 7).  Tiles are
